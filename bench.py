@@ -20,7 +20,14 @@ pairing-product-equation batch (BASELINE.json metric).
 One "step" = commit_and_prove + verify of every equation of the per-GPU batch (inputs resident in HBM).  Ranks
 barrier, time the same K steps, rank 0 reports MAX-over-ranks time; value = equations of all ranks / that time.
 
-Extra objects on the JSON line:
+A plain run does only what the headline figure needs: it builds the batch, warms up, times the K steps, writes the
+outputs of the last timed step if --dump-outputs DIR is given, and prints the JSON line.  Everything else -- the
+verdict checks on corrupted proofs after the timed steps, the rank-combined verdict check, the roofline step, the
+configurations under "also" and the CPU baseline -- runs with --full only.
+
+  --dump-outputs DIR   the arrays the last timed step handed its caller, as DIR/<name>.npy (see dump_outputs)
+
+Extra objects on the JSON line (--full):
   roofline      dominant kernel, HIP-event timed through the library's own hook; traffic = HBM bytes per launch from
                 the committed rocprofv3 PMC passes of the same configuration (profiles/<round>/traffic_*.json)
   cpu_baseline  oracle/gs_ref.c (CPU restatement of the reference path, NOT arkworks) timed on a bounded sample on
@@ -276,6 +283,39 @@ def pmc_traffic(tag, kernel_name):
     return None, None
 
 
+# --dump-outputs: at most this many bytes of .npy data per run (64 MB cap, room left for the headers); a larger output
+# is written as a fixed, seeded sample of its equations
+DUMP_BUDGET = 60 << 20
+DUMP_SEED = 20241220
+
+
+def dump_outputs(out_dir, parts, budget=DUMP_BUDGET):
+    """Write what the last timed step handed its caller: for each (prefix, workload, with_ok) in `parts`, the result
+    buffers xcoms / ycoms / pi / theta (boundary layout of include/gs_amd.h) as float64 arrays of their little-endian u32
+    words, one row per equation (exact: every word is below 2^53), and the per-equation verdict bytes `ok` (float32)
+    when the step wrote them.  The budget is shared evenly by the parts; a part whose equations do not all fit is
+    written for a sample of them, the same sorted, seeded choice of equations in every run (DUMP_SEED)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(len(parts), 1)
+    for prefix, w, with_ok in parts:
+        bufs = {k: getattr(w, k) for k in ("xcoms", "ycoms", "pi", "theta")}
+        per_eq = sum(t.numel() // w.N for t in bufs.values())  # bytes per equation; x 2 as float64 words
+        room = share - (4 * w.N if with_ok else 0)
+        count = min(w.N, max(room // (2 * per_eq), 1))
+        idx = np.arange(w.N)
+        if count < w.N:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(w.N, size=count, replace=False))
+        sel = torch.from_numpy(idx).to(w.xcoms.device)
+        for k, t in bufs.items():
+            rows = t.view(w.N, -1).index_select(0, sel).cpu().numpy()
+            np.save(os.path.join(out_dir, prefix + k + ".npy"), rows.view("<u4").astype(np.float64))
+        if with_ok:
+            np.save(os.path.join(out_dir, prefix + "ok.npy"), w.ok.cpu().numpy().astype(np.float32))
+
+
 def distinct_devices(dist, local, world, coll_dev):
     """number of distinct GPUs under the ranks of this job (ranks of one node: the set of their device ordinals)"""
     if dist is None:
@@ -323,8 +363,9 @@ class Bench:
         torch.cuda.synchronize()
 
     def run(self, log2n, curve=0, ty=0, mixed=False, mode="exact", steps=3, warmup=1, m=4, n=4, roofline=False,
-            seed_off=1):
-        """one configuration: returns the result dict (value = equations of ALL ranks per second)"""
+            seed_off=1, check=True, dump_dir=None):
+        """one configuration: returns the result dict (value = equations of ALL ranks per second).  check: verdicts on
+        corrupted proofs after the timed steps; dump_dir: write the outputs of the last timed step there."""
         import torch
 
         from groth_sahai_rs_amd.dist import allgather_accumulators, allreduce_failures
@@ -387,21 +428,32 @@ class Bench:
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
 
-        # ---- correctness of what was timed: all valid proofs accepted, corrupted ones rejected
-        for w in wls:
-            w.prove()
-            bad = set(w.corrupt())
-            w.verify()
-            eng.sync()
-            ok = w.ok.cpu().numpy()
-            expect = [0 if i in bad else 1 for i in range(w.N)]
-            assert ok.tolist() == expect, "verification verdicts wrong on the benchmark batch"
-            if mode == "rlc" and bad:
-                assert eng.gt_finalize(w.verify_rlc().cpu().numpy()) == 0, "batched verifier accepted a corrupted batch"
+        if dump_dir:
+            rp = "rank%d_" % rank if world > 1 else ""
+            names = ["ppe", "msmeg1", "msmeg2", "quad"]
+            dump_outputs(dump_dir, [(rp + (names[w.ty] + "_" if mixed else ""), w, mode == "exact") for w in wls],
+                         DUMP_BUDGET // world)
+            if mode == "rlc":  # the batched verifier hands back one verdict for the whole batch
+                import numpy as np
 
+                np.save(os.path.join(dump_dir, rp + "rlc_verdict.npy"), np.array([failures == 0], dtype=np.float32))
         res = {"value": N * world * steps / dt, "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": warmup,
                "equations_per_gpu": N, "workload": self.describe(log2n, curve, ty, mixed, mode, m, n)}
-        if dist is not None and mode == "exact":
+
+        # ---- correctness of what was timed (--full): all valid proofs accepted, corrupted ones rejected
+        if check:
+            for w in wls:
+                w.prove()
+                bad = set(w.corrupt())
+                w.verify()
+                eng.sync()
+                ok = w.ok.cpu().numpy()
+                expect = [0 if i in bad else 1 for i in range(w.N)]
+                assert ok.tolist() == expect, "verification verdicts wrong on the benchmark batch"
+                if mode == "rlc" and bad:
+                    assert eng.gt_finalize(w.verify_rlc().cpu().numpy()) == 0, "batched verifier accepted a corrupted batch"
+
+        if check and dist is not None and mode == "exact":
             # the rank-combined verdict sees a corrupted proof that exists on ONE rank only (the last): every rank must
             # come out of the all-reduce with exactly that rank's count
             for w in wls:
@@ -595,14 +647,17 @@ def inproc_main(args):
         torch.cuda.synchronize(d)
     dt = time.perf_counter() - t0
     assert all(w.ok.cpu().numpy().all() for w in wls), "a valid benchmark batch was rejected"
-    for w in wls:  # corrupted proofs are found, per shard
-        bad = set(w.corrupt())
-    me.verify_batch_dev(args.type, N, args.m, args.n, col("A"), col("B"), col("Gamma"), col("target"), col("xcoms"),
-                        col("ycoms"), col("pi"), col("theta"), col("ok"))
-    me.sync()
-    for w in wls:
-        ok = w.ok.cpu().numpy()
-        assert ok.tolist() == [0 if i in bad else 1 for i in range(w.N)], "verification verdicts wrong"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("shard%d_" % i, w, True) for i, w in enumerate(wls)])
+    if args.full:
+        for w in wls:  # corrupted proofs are found, per shard
+            bad = set(w.corrupt())
+        me.verify_batch_dev(args.type, N, args.m, args.n, col("A"), col("B"), col("Gamma"), col("target"), col("xcoms"),
+                            col("ycoms"), col("pi"), col("theta"), col("ok"))
+        me.sync()
+        for w in wls:
+            ok = w.ok.cpu().numpy()
+            assert ok.tolist() == [0 if i in bad else 1 for i in range(w.N)], "verification verdicts wrong"
     res = {"metric": "GS proofs+verifies/sec (BLS12-381 PPE batch)" if args.curve == 0 and args.type == 0 else
            "GS proofs+verifies/sec (curve %d type %d)" % (args.curve, args.type),
            "value": N * args.steps / dt, "unit": "proofs+verifies/s", "n_gpus": len(set(devices)), "steps": args.steps,
@@ -637,8 +692,13 @@ def main():
                     help="with --gpus N: ONE process drives the N GPUs through gs_ctx_create_multi and the device-pointer "
                          "family (gs_multi_*_dev: shards resident on their devices, persistent per-device threads) "
                          "instead of one process per GPU; GS_BENCH_SHARED=1 puts the N shards on GPU 0 (rehearsal)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the other single-GPU configurations")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the verdict checks after the timed steps, the roofline step, "
+                         "the other single-GPU configurations (\"also\") and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step to DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the other single-GPU configurations")
     ap.add_argument("--cpu-sample", type=int, default=0, help="CPU-baseline sample units (0 = auto, ~20 s)")
     args = ap.parse_args()
 
@@ -688,7 +748,7 @@ def main():
 
     b = Bench(args, dist, rank, world, local, dev, coll_dev)
     main_res = b.run(args.log2n, args.curve, args.type, args.mixed, args.mode, args.steps, args.warmup, args.m, args.n,
-                     roofline=True)
+                     roofline=args.full, check=args.full, dump_dir=args.dump_outputs)
 
     res = {
         "metric": "GS proofs+verifies/sec (BLS12-381 PPE batch)" if args.curve == 0 and args.type == 0 else
@@ -718,9 +778,10 @@ def main():
     if "rank_combined_check" in main_res:
         res["config"]["rank_combined_check"] = main_res["rank_combined_check"]
     if rank == 0:
-        res["roofline"] = main_res.get("roofline")
+        if args.full:
+            res["roofline"] = main_res.get("roofline")
         default_cfg = args.curve == 0 and args.type == 0 and not args.mixed and args.mode == "exact"
-        if world == 1 and not args.no_also and default_cfg:
+        if args.full and world == 1 and not args.no_also and default_cfg:
             also = {}
             for tag, kw, st in (("2p12_ppe", dict(log2n=12), 10), ("2p12_mixed", dict(log2n=12, mixed=True), 10),
                                 ("2p16_mixed", dict(log2n=16, mixed=True), 3),
@@ -740,7 +801,7 @@ def main():
             also["2p16_ppe_hostreg"] = b.run_hostptr(16, steps=3, registered=True)
             also["2p12_ppe_hostreg"] = b.run_hostptr(12, steps=20, registered=True)
             res["also"] = also
-        if not args.no_cpu:  # rank 0 times the CPU baseline on the host cores it is granted, at every N
+        if args.full and not args.no_cpu:  # rank 0 times the CPU baseline on the host cores it is granted, at every N
             threads, _ = host_cores()
             sample = args.cpu_sample or max(128 * threads, 256)   # ~10-30 s of CPU work on the granted host cores
             res["cpu_baseline"] = cpu_baseline(sample, threads)

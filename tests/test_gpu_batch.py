@@ -95,8 +95,8 @@ def test_bench_two_rank_rehearsal(mode, launch):
 
     env = dict(os.environ, GS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
-    tail = [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log2n", "8", "--no-cpu",
-            "--mode", mode]
+    tail = [os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--log2n", "8", "--full",
+            "--no-cpu", "--mode", mode]
     if launch == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", "29533" if mode == "exact" else "29534"] + tail
@@ -125,7 +125,7 @@ def test_bench_inproc_rehearsal():
     env = dict(os.environ, GS_BENCH_SHARED="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "3", "--inproc", "--steps", "1", "--warmup", "1",
-           "--log2n", "8"]
+           "--log2n", "8", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -150,7 +150,7 @@ def test_bench_driver_line_rehearsal_four_ranks_and_eight_shards():
     env = dict(os.environ, GS_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--log2n", "10",
-           "--cpu-sample", "32"]
+           "--full", "--cpu-sample", "32"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -165,7 +165,7 @@ def test_bench_driver_line_rehearsal_four_ranks_and_eight_shards():
     env = dict(os.environ, GS_BENCH_SHARED="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "8", "--inproc", "--steps", "2", "--warmup", "1",
-           "--log2n", "15"]
+           "--log2n", "15", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
@@ -183,6 +183,34 @@ def test_bench_refuses_fewer_ranks_than_requested():
            "--log2n", "6", "--no-cpu"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=200)
     assert r.returncode != 0 and "--gpus 4" in (r.stderr + r.stdout)
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` line carries the headline keys and nothing that --full adds; --dump-outputs writes
+    the result buffers of the last timed step (u32 words as float64, verdicts as float32), identical for two runs with
+    the same batch arguments (seeded inputs), every honest proof accepted."""
+    import json
+    import subprocess
+
+    outs = []
+    for steps in (2, 1):
+        d = tmp_path / ("steps%d" % steps)
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--log2n", "8", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=280)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.strip().splitlines() if l.startswith("{")][-1])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(line)
+        assert line["steps"] == steps and not {"roofline", "also", "cpu_baseline"} & set(line)
+        assert line["value"] == pytest.approx(256 / (line["ms_per_step"] / 1e3), rel=1e-6)
+        arrs = {p.stem: np.load(p) for p in d.glob("*.npy")}
+        assert sorted(arrs) == ["ok", "pi", "theta", "xcoms", "ycoms"]
+        assert arrs["ok"].dtype == np.float32 and arrs["ok"].shape == (256,) and (arrs["ok"] == 1).all()
+        for k in ("pi", "theta", "xcoms", "ycoms"):
+            assert arrs[k].dtype == np.float64 and arrs[k].shape[0] == 256 and arrs[k].any()
+        outs.append(arrs)
+    for k in outs[0]:
+        assert np.array_equal(outs[0][k], outs[1][k]), k
 
 
 @pytest.mark.parametrize("cname,cid", [("bls12_381", 0), ("bn254", 1)])

@@ -5,7 +5,7 @@ OUT=$1; ARGS=$2; shift 2
 mkdir -p "$OUT"
 for v in "$@"; do
   if [ "$v" = main ]; then unset GS_AMD_LIB; else export GS_AMD_LIB=$PWD/groth_sahai_rs_amd/lib/var/$v.so; fi
-  timeout -k 10 300 python3 bench.py --no-also --no-cpu $ARGS > "$OUT/ab_$v.json" 2> "$OUT/ab_$v.err" || { echo "$v FAILED"; tail -5 "$OUT/ab_$v.err"; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-also --no-cpu $ARGS > "$OUT/ab_$v.json" 2> "$OUT/ab_$v.err" || { echo "$v FAILED"; tail -5 "$OUT/ab_$v.err"; exit 1; }
   python3 - "$OUT/ab_$v.json" "$v" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))

@@ -6,7 +6,7 @@ i=0
 for e in "$@"; do
   i=$((i+1))
   if [ "$e" = "-" ]; then e=""; fi
-  env $e timeout -k 10 300 python3 bench.py --no-also --no-cpu $ARGS > "$OUT/env_$i.json" 2> "$OUT/env_$i.err" || { echo "$e FAILED"; tail -5 "$OUT/env_$i.err"; exit 1; }
+  env $e timeout -k 10 300 python3 bench.py --full --no-also --no-cpu $ARGS > "$OUT/env_$i.json" 2> "$OUT/env_$i.err" || { echo "$e FAILED"; tail -5 "$OUT/env_$i.err"; exit 1; }
   python3 - "$OUT/env_$i.json" "${e:-planned}" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))

@@ -22,7 +22,7 @@ ev.sort()
 # the last k_prep_prove starts the last call pair
 starts = [i for i, e in enumerate(ev) if "k_prep_prove" in e[2]]
 # optional second argument: which k_prep_prove launch opens the listing (-1 = the last one, the default; -2 = the one
-# before it: under bench.py the last step is the per-kernel profiling step, which does not merge a mixed call's parts)
+# before it: under bench.py --full the last step is the per-kernel profiling step, which does not merge a mixed call's parts)
 i0 = starts[int(sys.argv[2]) if len(sys.argv) > 2 else -1]
 # copies that precede it belong to the call too: walk back over copies within 20 ms
 while i0 > 0 and ev[i0 - 1][2].startswith("C") and ev[i0][0] - ev[i0 - 1][0] < 20e6:

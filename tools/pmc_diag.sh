@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 cd /tmp
 pass() {  # name, counters...
   local n=$1; shift
-  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/$n -- python3 $R/bench.py --steps 1 --warmup 0 --no-cpu --no-also $BARGS > /dev/null 2>$O/$n.err || { echo "pass $n failed"; tail -5 $O/$n.err; }
+  rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/$n -- python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu --no-also $BARGS > /dev/null 2>$O/$n.err || { echo "pass $n failed"; tail -5 $O/$n.err; }
   echo "pass $n done"
 }
 BARGS="$*"
