@@ -35,6 +35,7 @@ SYMBOLS = [
     "gs_ctx_create_multi_ex", "gs_multi_exchange_note", "gs_multi_sync", "gs_multi_set_option", "gs_multi_prove_batch_dev",
     "gs_multi_verify_batch_dev", "gs_multi_verify_batch_rlc_dev", "gs_gt_finalize_dev",
     "gs_prove_mixed_dev", "gs_prove_mixed", "gs_verify_mixed_dev", "gs_verify_mixed",
+    "gs_rerandomize_batch_dev", "gs_rerandomize_batch", "gs_rerandomize_statement_dev", "gs_rerandomize_statement",
 ]
 GS_MIXED_MAX = 8
 GS_MULTI_SHARED_DEVICES = 1
@@ -301,6 +302,45 @@ class Engine:
                                           _p(pi), _p(th)))
         return dict(xcoms=xc, ycoms=yc, pi=pi, theta=th)
 
+    def _check_rerand(self, fn, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T, outs=(None,) * 4,
+                      shared=False):
+        if not (0 <= ty <= 3) or m < 1 or n < 1:
+            raise GsError(1, "%s: bad equation type or empty variable list" % fn)
+        sh = self.shape(ty)
+        kx, ky, sx, sy = sh["kx"], sh["ky"], sh["sx"], sh["sy"]
+        V = 1 if shared else N  # a Statement: one copy of the commitments and of R', S'
+        xo, yo, po, to = outs
+        _need(fn, [("A", A, N * n * sx), ("B", B, N * m * sy), ("Gamma", Gamma, N * m * n * self.FR),
+                   ("xcoms", xcoms, V * m * self.COM1), ("ycoms", ycoms, V * n * self.COM2),
+                   ("pi", pi, N * kx * self.COM2), ("theta", theta, N * ky * self.COM1),
+                   ("R", R, V * m * kx * self.FR), ("S", S, V * n * ky * self.FR), ("T", T, N * ky * kx * self.FR),
+                   ("xcoms_out", xo, V * m * self.COM1), ("ycoms_out", yo, V * n * self.COM2),
+                   ("pi_out", po, N * kx * self.COM2), ("theta_out", to, N * ky * self.COM1)])
+
+    def _rerand_host(self, fn, shared, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T):
+        sh = self.shape(ty)
+        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        args = list(map(u8, (A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T)))
+        self._check_rerand(fn, ty, N, m, n, *args, shared=shared)
+        V = 1 if shared else N
+        xo, yo = self._out(V * m * self.COM1), self._out(V * n * self.COM2)
+        po, to = self._out(N * sh["kx"] * self.COM2), self._out(N * sh["ky"] * self.COM1)
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, ctypes.c_size_t(N), m, n, *[_p(a) for a in args], _p(xo), _p(yo),
+                                        _p(po), _p(to)))
+        return dict(xcoms=xo, ycoms=yo, pi=po, theta=to)
+
+    def rerandomize_batch(self, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T):
+        """Fresh commitments and proofs for N proven equations from fresh randomness R', S', T' (gs_rerandomize_batch):
+        no witness.  R', S', T' must be uniform, fresh and secret."""
+        return self._rerand_host("gs_rerandomize_batch", False, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
+                                 R, S, T)
+
+    def rerandomize_statement(self, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T):
+        """A Statement's shared commitments xcoms[m], ycoms[n] (updated once with R'[m], S'[n]) and its E proofs
+        (gs_rerandomize_statement)."""
+        return self._rerand_host("gs_rerandomize_statement", True, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
+                                 R, S, T)
+
     def verify_batch(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, ok=None):
         u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         if ok is None:
@@ -433,6 +473,23 @@ class Engine:
         self._chk(self.lib.gs_prove_batch_dev(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(X), _p(Y), _p(A), _p(B),
                                               _p(Gamma), _p(R), _p(S), _p(T), _p(xcoms), _p(ycoms), _p(pi),
                                               _p(theta)))
+
+    def _rerand_dev(self, fn, shared, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T, xcoms_out,
+                    ycoms_out, pi_out, theta_out):
+        outs = (xcoms_out, ycoms_out, pi_out, theta_out)
+        self._check_rerand(fn, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T, outs, shared=shared)
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, ctypes.c_size_t(N), m, n,
+                                        *[_p(a) for a in (A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T) + outs]))
+
+    def rerandomize_batch_dev(self, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out,
+                              pi_out, theta_out):
+        self._rerand_dev("gs_rerandomize_batch_dev", False, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T,
+                         xcoms_out, ycoms_out, pi_out, theta_out)
+
+    def rerandomize_statement_dev(self, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T, xcoms_out,
+                                  ycoms_out, pi_out, theta_out):
+        self._rerand_dev("gs_rerandomize_statement_dev", True, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S,
+                         T, xcoms_out, ycoms_out, pi_out, theta_out)
 
     def verify_batch_dev(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, ok):
         self._check_verify("gs_verify_batch_dev", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)

@@ -546,6 +546,7 @@ static inline int out_ready(gs_ctx* c, unsigned mask) { return c->pipe ? c->pipe
 // array slots of the host-pointer entry points
 enum { PI_X = 0, PI_Y, PI_A, PI_B, PI_G, PI_R, PI_S, PI_T, PO_XC, PO_YC, PO_PI, PO_TH };           // prove
 enum { VI_A = 0, VI_B, VI_G, VI_TG, VI_XC, VI_YC, VI_PI, VI_TH, VO_OK };                            // verify
+enum { RI_A = 0, RI_B, RI_G, RI_R, RI_S, RI_T, RI_XC, RI_YC, RI_PI, RI_TH, RO_XC, RO_YC, RO_PI, RO_TH };  // rerandomize
 #define BIT(i) (1u << (i))
 
 // the batch size the lane-shape planners should fill the chip for: the part's own, or (mixed calls, whose parts'
@@ -1217,6 +1218,51 @@ static void build_side(SidePlan& sp, bool want_coms, int nv, int nc, bool group,
   sp.nslots = slot;
 }
 
+// Build the plan of one side of a RERANDOMIZATION (no witness: the variables are known only through their old
+// commitments, which enter as variable-base terms -- both components of each -- and as affine addends).
+//  nv, nc, group, kc, npf   as in build_side; npf = 0 plans the commitments alone (a Statement's, made once)
+//  pool offsets: rc (nv x kc fresh commit randomness), cs (nc x npf: S' for the G1 side / R' for the G2 side, [j*npf + l]),
+//  ph (npf x nv: PHI' / PSI'), f0 (npf x kc: T' / OMEGA'), sg (npf: SIG' = S'^T a / RHO' = R'^T b, scalar sides)
+//  arrays: 0 = old commitments (2 nv points: component c of commitment i is point 2 i + c), 1 = constants (group),
+//  2 = old proof elements (2 npf points)
+//    com'_i.c   = com_i.c + sum_a rand_ia key_a.c                                  (fixed + addend)
+//    pf'_l.c    = pf_l.c + f0_l . key.c [+ sg_l W.c] + sum_i ph_li com_i.c [+ (c = 1) sum_j cs_jl const_j]
+static void build_rerand_side(SidePlan& sp, bool want_coms, int nv, int nc, bool group, int kc, int npf, int rc, int cs,
+                              int ph, int f0, int sg) {
+  int slot = 0;
+  if (want_coms) {
+    for (int i = 0; i < nv; i++) {
+      int s_begin = slot;
+      for (int c = 0; c < 2; c++) {
+        if (group)
+          sp.fix.push_back(mkfix(rc + 2 * i, tb_u(0, c), rc + 2 * i + 1, tb_u(1, c), 0, 2 * i + c, slot++));
+        else
+          sp.fix.push_back(mkfix(rc + i, tb_u(0, c), 0, 0xFF, 0, 2 * i + c, slot++));
+      }
+      sp.red.push_back(mkred(s_begin, s_begin + 1, s_begin + 1, s_begin + 2, 0, i));
+    }
+    sp.ncom = nv;
+  }
+  for (int l = 0; l < npf; l++) {
+    int b[2], e[2];
+    for (int c = 0; c < 2; c++) {
+      b[c] = slot;
+      if (group)
+        sp.fix.push_back(mkfix(f0 + l * 2, tb_u(0, c), f0 + l * 2 + 1, tb_u(1, c), 2, 2 * l + c, slot++));
+      else
+        sp.fix.push_back(mkfix(sg + l, tb_w(c), f0 + l, tb_u(0, c), 2, 2 * l + c, slot++));
+      std::vector<VarTask> terms;
+      if (group && c == 1)  // iota(const) = (O, const)
+        for (int j = 0; j < nc; j++) terms.push_back(mkvar(cs + j * npf + l, 1, j, 0));
+      for (int i = 0; i < nv; i++) terms.push_back(mkvar(ph + l * nv + i, 0, 2 * i + c, 0));
+      add_var_terms(sp, terms, slot);
+      e[c] = slot;
+    }
+    sp.red.push_back(mkred(b[0], e[0], b[1], e[1], 1, l));
+  }
+  sp.nslots = slot;
+}
+
 // the reduction launch of a side, kept back so that the caller can run the two sides' reductions side by side
 struct RedLaunch {
   std::string name, tag;
@@ -1669,6 +1715,89 @@ template <class C> struct Impl {
       hipStreamWaitEvent(c->stream, c->sev[5], 0);
     }
     return GS_OK;
+  }
+
+  // rerandomization of commitments and proofs without the witness, for all four types:
+  //   c' = c + R' U_x,  d' = d + S' V_y,
+  //   pi'    = pi + R'^T iota2(B) + (R'^T Gamma) d + (R'^T Gamma S' - T'^T) V_y
+  //   theta' = theta + S'^T iota1(A) + (S'^T Gamma^T) c + T' U_x          (c, d: the OLD commitments)
+  // The scalars are the prover's own with no witness scalars: k_prep_prove with xs = ys = NULL computes
+  // Psi' = R'^T Gamma, Phi' = S'^T Gamma^T, Omega' = Psi' S' - T'^T, rho' = R'^T b, sigma' = S'^T a.
+  // shared: a Statement -- ONE copy of c, d, R', S' (stride 0) for all N equations; the commitments are updated once.
+  static int rerandomize(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                         const void* xc, const void* yc, const void* pi, const void* th, const void* R, const void* Sm,
+                         const void* T, void* xco, void* yco, void* pio, void* tho, bool shared) {
+    bool xg = x_is_group(ty), yg = y_is_group(ty);
+    int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
+    PoolMap pm = prove_pool(m, n, kx, ky);
+    void* pool;
+    RC(scratch(c, "rerand.pool", N * pm.total * sizeof(S), &pool));
+    RangeGuard rg_all("gs.rerandomize");
+    RC(need(c, BIT(RI_G) | BIT(RI_R) | BIT(RI_S) | BIT(RI_T) | (xg ? 0u : BIT(RI_A)) | (yg ? 0u : BIT(RI_B))));
+    if (wide_prep(m, n)) {
+      int W = m * kx + n * ky + ky * kx + m + n + kx * n + ky * m;
+      RC(launch_seg<k_prep_prove_wide_a<C>>(c, "k_prep_rerand.a", N * (size_t)W, 64, N * (size_t)W, W, m, n, kx, ky,
+                (const S*)G, (const S*)R, (const S*)Sm, (const S*)T, (const S*)nullptr, (const S*)nullptr, pm, (S*)pool,
+                shared ? 1 : 0));
+      size_t tb = N * (size_t)(kx * ky + kx + ky);
+      RC(launch_seg<k_prep_prove_wide_b<C>>(c, "k_prep_rerand.b", tb, 64, tb, m, n, kx, ky, (const S*)R, (const S*)Sm,
+                (const S*)T, (const S*)nullptr, (const S*)nullptr, xg ? nullptr : (const S*)A,
+                yg ? nullptr : (const S*)B, pm, (S*)pool, shared ? 1 : 0));
+    } else {
+      RC(launch_seg<k_prep_prove<C>>(c, "k_prep_rerand", N, 64, N, m, n, kx, ky, (const S*)G, (const S*)R, (const S*)Sm,
+                (const S*)T, (const S*)nullptr, (const S*)nullptr, xg ? nullptr : (const S*)A,
+                yg ? nullptr : (const S*)B, pm, (S*)pool, shared ? 1 : 0));
+    }
+    // one side over NN equations: the commitments (coms) and / or the proof elements (proofs) of that side
+    auto side = [&](auto* ftag, size_t NN, bool coms, bool proofs, const char* tag) -> int {
+      typedef std::remove_pointer_t<decltype(ftag)> F;
+      constexpr bool g2 = std::is_same<F, F2>::value;
+      const bool grp = g2 ? yg : xg;
+      const int nv = g2 ? n : m, nc = g2 ? m : n, kc = g2 ? ky : kx, npf = g2 ? kx : ky, np = proofs ? npf : 0;
+      const uint32_t zp = (uint32_t)(g2 ? Z::G2 : Z::G1);
+      SidePlan sp;
+      sp.tm = np ? pick_tm(c, fillN(c, NN), grp ? nv + nc : nv, 2 * np, g2, np) : 1;
+      if (g2)
+        build_rerand_side(sp, coms, nv, nc, grp, kc, np, pm.SC, pm.RC, pm.PSI, pm.OM, pm.RHO);
+      else
+        build_rerand_side(sp, coms, nv, nc, grp, kc, np, pm.RC, pm.SC, pm.PHI, pm.TC, pm.SIG);
+      ArrTab arrs;
+      memset(&arrs, 0, sizeof arrs);
+      arrs.base[0] = (const uint8_t*)(g2 ? yc : xc);
+      arrs.stride[0] = shared ? 0u : (uint32_t)nv * 2 * zp;
+      if (grp) {
+        arrs.base[1] = (const uint8_t*)(g2 ? B : A);
+        arrs.stride[1] = (uint32_t)nc * zp;
+      }
+      arrs.base[2] = (const uint8_t*)(g2 ? pi : th);
+      arrs.stride[2] = (uint32_t)npf * 2 * zp;
+      OutTab outs;
+      memset(&outs, 0, sizeof outs);
+      outs.base[0] = (uint8_t*)(g2 ? yco : xco);
+      outs.stride[0] = (uint32_t)nv * 2 * zp;
+      outs.base[1] = (uint8_t*)(g2 ? pio : tho);
+      outs.stride[1] = (uint32_t)npf * 2 * zp;
+      RangeGuard rg(g2 ? "gs.rerandomize.g2" : "gs.rerandomize.g1");
+      const unsigned in_com = BIT(g2 ? RI_YC : RI_XC), in_pf = BIT(g2 ? RI_PI : RI_TH), in_k = BIT(g2 ? RI_B : RI_A);
+      const unsigned masks[4] = {in_com | (proofs ? in_pf : 0u), proofs ? in_k : 0u, coms ? BIT(g2 ? RO_YC : RO_XC) : 0u,
+                                 proofs ? BIT(g2 ? RO_PI : RO_TH) : 0u};
+      const void* tab = g2 ? c->tabs->tab16_g2.p : c->tabs->tab16_g1.p;
+      return run_side<C, F>(c, tag, NN, sp, arrs, (const S*)pool, pm.total, (const Aff<F>*)tab, outs, nullptr, nullptr,
+                            nullptr, nullptr, masks);
+    };
+    if (shared) {  // the Statement's commitments once (equation 0 of the pool holds R', S'), then the E proofs
+      RC(side((F1*)nullptr, 1, true, false, ".rc1"));
+      RC(side((F2*)nullptr, 1, true, false, ".rc2"));
+      RC(side((F1*)nullptr, N, false, true, ".rg1"));
+      return side((F2*)nullptr, N, false, true, ".rg2");
+    }
+    // (host-pointer calls: the G2 side first, as in prove -- theta is then the last output to cross PCIe)
+    if (c->pipe && N >= 16 * c->simd_slots) {
+      RC(side((F2*)nullptr, N, true, true, ".rg2"));
+      return side((F1*)nullptr, N, true, true, ".rg1");
+    }
+    RC(side((F1*)nullptr, N, true, true, ".rg1"));
+    return side((F2*)nullptr, N, true, true, ".rg2");
   }
 
   // commitments only (commit.rs:59-256): a "prove" side with no proof elements
@@ -3176,6 +3305,95 @@ int gs_verify_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* A
   RC(verify_host_stage(c, a, hp));
   RC(verify_host_run(c, a, hp));
   return hp.finish();
+}
+
+// ---- rerandomize: fresh commitments and proofs from old ones, without the witness -----------------------------
+struct RerandArgs {
+  int ty;
+  size_t N;
+  int m, n;
+  const void *A, *B, *G, *xc, *yc, *pi, *th, *R, *S, *T;
+  void *xco, *yco, *pio, *tho;
+  bool shared;  // a Statement: ONE copy of the commitments and of R', S' for all N equations
+};
+static int rerand_check(gs_ctx* c, const RerandArgs& a) {
+  RC(check_ctx(c, true));
+  RC(check_shape(c, a.ty, a.m, a.n));
+  if (a.N == 0) return GS_OK;
+  if (!a.A || !a.B || !a.G || !a.xc || !a.yc || !a.pi || !a.th || !a.R || !a.S || !a.T || !a.xco || !a.yco || !a.pio ||
+      !a.tho)
+    return fail(c, GS_ERR_ARG, "null pointer");
+  return GS_OK;
+}
+// byte sizes of the arrays, in the order A, B, G, xc, yc, pi, th, R, S, T, xco, yco, pio, tho
+static void rerand_sizes(gs_ctx* c, const RerandArgs& a, size_t sz[14]) {
+  size_t fq = sz_fq(c->curve), N = a.N, V = a.shared ? 1 : a.N;
+  bool xg = x_is_group(a.ty), yg = y_is_group(a.ty);
+  size_t kx = xg ? 2 : 1, ky = yg ? 2 : 1, m = (size_t)a.m, n = (size_t)a.n;
+  size_t sx = xg ? 2 * fq : SZ_FR, sy = yg ? 4 * fq : SZ_FR;
+  const size_t v[14] = {N * n * sx,          N * m * sy,          N * m * n * SZ_FR,  V * m * 4 * fq, V * n * 8 * fq,
+                        N * kx * 8 * fq,     N * ky * 4 * fq,     V * m * kx * SZ_FR, V * n * ky * SZ_FR,
+                        N * ky * kx * SZ_FR, V * m * 4 * fq,      V * n * 8 * fq,     N * kx * 8 * fq, N * ky * 4 * fq};
+  for (int i = 0; i < 14; i++) sz[i] = v[i];
+}
+static int rerand_dev(gs_ctx* c, const RerandArgs& a) {
+  RC(rerand_check(c, a));
+  if (a.N == 0) return GS_OK;
+  return DISPATCH(c, rerandomize(c, a.ty, a.N, a.m, a.n, a.A, a.B, a.G, a.xc, a.yc, a.pi, a.th, a.R, a.S, a.T, a.xco,
+                                 a.yco, a.pio, a.tho, a.shared));
+}
+static int rerand_host(gs_ctx* c, const RerandArgs& a) {
+  RC(rerand_check(c, a));
+  if (a.N == 0) return GS_OK;
+  size_t sz[14];
+  rerand_sizes(c, a, sz);
+  const void* p[14] = {a.A, a.B, a.G, a.xc, a.yc, a.pi, a.th, a.R, a.S, a.T, a.xco, a.yco, a.pio, a.tho};
+  // outputs do not alias inputs or each other (the device reads old commitments after it has written new ones)
+  for (int o = 10; o < 14; o++)
+    for (int i = 0; i < 14; i++) {
+      if (i == o) continue;
+      uintptr_t x = (uintptr_t)p[o], y = (uintptr_t)p[i];
+      if (x < y + sz[i] && y < x + sz[o]) return fail(c, GS_ERR_ARG, "rerandomize: an output overlaps another array");
+    }
+  HostPipe hp(c);
+  // staging order = the order rerandomize() asks for them: scalars, then the G2 side's arrays, then the G1 side's
+  static const int slot[14] = {RI_A, RI_B, RI_G, RI_XC, RI_YC, RI_PI, RI_TH, RI_R, RI_S, RI_T, RO_XC, RO_YC, RO_PI, RO_TH};
+  for (int i = 0; i < 10; i++) hp.in(slot[i], p[i], sz[i]);
+  for (int i = 10; i < 14; i++) hp.out(slot[i], (void*)p[i], sz[i]);
+  static const int order[] = {RI_G, RI_R, RI_S, RI_T, RI_B, RI_A, RI_YC, RI_PI, RI_XC, RI_TH};
+  RC(hp.begin(order, 10));
+  RerandArgs d{a.ty, a.N, a.m, a.n, hp.dev(RI_A), hp.dev(RI_B), hp.dev(RI_G), hp.dev(RI_XC), hp.dev(RI_YC),
+               hp.dev(RI_PI), hp.dev(RI_TH), hp.dev(RI_R), hp.dev(RI_S), hp.dev(RI_T), hp.dev(RO_XC), hp.dev(RO_YC),
+               hp.dev(RO_PI), hp.dev(RO_TH), a.shared};
+  RC(rerand_dev(c, d));
+  return hp.finish();
+}
+int gs_rerandomize_batch_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                             const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
+                             const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
+                             void* theta_out) {
+  return rerand_dev(c, RerandArgs{ty, N, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
+                                  theta_out, false});
+}
+int gs_rerandomize_batch(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                         const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
+                         const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out, void* theta_out) {
+  return rerand_host(c, RerandArgs{ty, N, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
+                                   theta_out, false});
+}
+int gs_rerandomize_statement_dev(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
+                                 const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
+                                 const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
+                                 void* theta_out) {
+  return rerand_dev(c, RerandArgs{ty, E, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
+                                  theta_out, true});
+}
+int gs_rerandomize_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
+                             const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
+                             const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
+                             void* theta_out) {
+  return rerand_host(c, RerandArgs{ty, E, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
+                                   theta_out, true});
 }
 
 // ---- helpers / hooks -----------------------------------------------------------

@@ -8,6 +8,7 @@ top of the C ABI (same names, argument meaning and error behaviour):
         .commit_and_prove(xvars, yvars, crs, rng) -> CProof                src/prover/prove.rs:29-52
         .prove(xvars, yvars, xcoms, ycoms, crs, rng) -> EquProof
         .verify(com_proof, crs) -> bool                                    src/verifier.rs:18-21
+    rerandomize(equ, com_proof, crs, rng) -> CProof                      (new) fresh commitments and proof, no witness
     EquProof {pi, theta, equ_type, rand}, CProof {xcoms, ycoms, equ_proofs} prove.rs:55-69
 
 Values are numpy uint64 limb arrays in the boundary layout of include/gs_amd.h
@@ -205,6 +206,62 @@ class _Equation:
                                      _cat(com_proof.xcoms.coms, 0), _cat(com_proof.ycoms.coms, 0), _cat(pf.pi, 0),
                                      _cat(pf.theta, 0))
         return bool(ok[0])
+
+
+# scalar field orders (BLS12-381, BN254): the rand bookkeeping of rerandomize() is host-side Fr arithmetic on small
+# matrices; Montgomery form with R = 2^256 (include/gs_amd.h)
+_FR_ORDER = (0x73EDA753299D7D483339D80809A1D80553BDA402FFFE5BFEFFFFFFFF00000001,
+             0x30644E72E131A029B85045B68181585D2833E84879B9709143E1F593F0000001)
+
+
+def _fr_int(v, r):  # Montgomery limbs -> canonical integer
+    a = np.asarray(v, dtype=np.uint64).reshape(-1)
+    return sum(int(a[i]) << (64 * i) for i in range(4)) * pow(1 << 256, -1, r) % r
+
+
+def _fr_limbs(x, r):  # canonical integer -> Montgomery limbs
+    y = (x << 256) % r
+    return np.array([(y >> (64 * i)) & 0xFFFFFFFFFFFFFFFF for i in range(4)], dtype=np.uint64)
+
+
+def rerandomize(equ, com_proof, crs, rng):
+    """A fresh-looking CProof for `equ` from `com_proof` alone (gs_rerandomize_batch): no witness.  Draws R' (m x kx),
+    then S' (n x ky), then T' (ky x kx) from `rng` -- the reference's draw order -- and returns commitments and proof
+    that verify against the same equation and are distributed like a fresh proof of the same witness.  When the input
+    carries its randomness (mirror objects always do), the result carries R + R', S + S' and T + T' + S'^T Gamma^T R:
+    exactly what commit_and_prove with that randomness would have produced, byte for byte."""
+    assert len(com_proof.equ_proofs) == 1
+    pf = com_proof.equ_proofs[0]
+    assert equ.get_type() == pf.equ_type
+    kx, ky = equ._kxky()
+    m, n = len(com_proof.xcoms.coms), len(com_proof.ycoms.coms)
+    assert m >= 1 and n >= 1
+    equ._check_statement_shape(m, n)
+    # lengths that come from the wire are checked before a pointer crosses the C ABI
+    assert len(pf.pi) == kx and len(pf.theta) == ky
+    R1 = [[rng.fr() for _ in range(kx)] for _ in range(m)]
+    S1 = [[rng.fr() for _ in range(ky)] for _ in range(n)]
+    T1 = [[rng.fr() for _ in range(kx)] for _ in range(ky)]
+    out = crs.engine.rerandomize_batch(equ.TYPE, 1, m, n, _cat(equ.a_consts, 0), _cat(equ.b_consts, 0),
+                                       _flat_mat(equ.gamma), _cat(com_proof.xcoms.coms, 0),
+                                       _cat(com_proof.ycoms.coms, 0), _cat(pf.pi, 0), _cat(pf.theta, 0),
+                                       _flat_mat(R1), _flat_mat(S1), _flat_mat(T1))
+    xr, yr, tr = com_proof.xcoms.rand, com_proof.ycoms.rand, pf.rand
+    if xr is not None and yr is not None and tr is not None:
+        r = _FR_ORDER[crs.engine.curve]
+        I = lambda mat: [[_fr_int(v, r) for v in row] for row in mat]
+        L = lambda mat: [[_fr_limbs(v, r) for v in row] for row in mat]
+        R0, R1i, S0, S1i, T0, T1i, G = I(xr), I(R1), I(yr), I(S1), I(tr), I(T1), I(equ.gamma)
+        xr = L([[(R0[i][a] + R1i[i][a]) % r for a in range(kx)] for i in range(m)])
+        yr = L([[(S0[j][b] + S1i[j][b]) % r for b in range(ky)] for j in range(n)])
+        # T'' = T + T' + S'^T Gamma^T R   (ky x kx)
+        tr = L([[(T0[l][k] + T1i[l][k] + sum(S1i[j][l] * G[i][j] * R0[i][k] for i in range(m) for j in range(n))) % r
+                 for k in range(kx)] for l in range(ky)])
+    else:
+        xr = yr = tr = None
+    xcoms = Commit1(_split(out["xcoms"], m), xr)
+    ycoms = Commit2(_split(out["ycoms"], n), yr)
+    return CProof(xcoms, ycoms, [EquProof(_split(out["pi"], kx), _split(out["theta"], ky), equ.TYPE, tr)])
 
 
 class PPE(_Equation):

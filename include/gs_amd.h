@@ -9,6 +9,8 @@
  *                             xcoms/ycoms != NULL src/prover/prove.rs:72-90,175-193,278-296,383-408 (commit_and_prove)
  *   gs_verify_batch        <- src/verifier.rs:23-157       (Verifiable::verify, exact semantics, bool per equation)
  *   gs_verify_batch_rlc    <- (new) batched pairing-product check, one final exponentiation per batch
+ *   gs_rerandomize_batch   <- (new) rerandomization of commitments and proofs without the witness (the same
+ *                             algebra as src/prover/prove.rs:92-171,195-274,298-379,409-488 applied to fresh randomness)
  *   gs_mat_left_mul_com1/2 <- src/data_structures.rs:696-742 (Mat::left_mul on Matrix<Com1/Com2>)
  *   gs_pairing_sum         <- src/data_structures.rs:494-502 (ComT::pairing_sum)
  *   gs_set_crs             <- consumes src/generator.rs:35-42 (struct CRS)
@@ -203,6 +205,44 @@ int gs_prove_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const 
 int gs_prove_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y, const void* A,
                        const void* B, const void* Gamma, const void* R, const void* S, const void* T, void* xcoms,
                        void* ycoms, void* pi, void* theta);
+
+/* ---- rerandomize (no witness) --------------------------------------------- */
+/* From commitments xcoms[N][m] (Com1), ycoms[N][n] (Com2) and proofs pi[N][kx], theta[N][ky] of N equations, and fresh
+ * randomness R'[N][m][kx], S'[N][n][ky], T'[N][ky][kx] (the layouts of gs_prove_batch), new commitments and proofs
+ * that verify against the same equations, WITHOUT the witness X, Y:
+ *   c'_i   = c_i + sum_a R'_ia U_x,a                 d'_j = d_j + sum_b S'_jb V_y,b
+ *   pi'    = pi + R'^T iota2(B) + (R'^T Gamma) d + (R'^T Gamma S' - T'^T) V_y        (d = the OLD commitments)
+ *   theta' = theta + S'^T iota1(A) + (S'^T Gamma^T) c + T' U_x                        (c = the OLD commitments)
+ * U_x = (u0, u1) for G1 variables, (u0) for scalar ones; V_y likewise with v; iota1/iota2 are the maps the prover
+ * applies to A and B.  Starting from gs_prove_batch(X, Y, R, S, T), the output is BYTE-IDENTICAL to
+ * gs_prove_batch(X, Y, R + R', S + S', T + T' + S'^T Gamma^T R) (commitments included), and the verifier's verdict is
+ * unchanged: valid proofs stay valid, invalid ones stay invalid (nothing is verified here).
+ * RANDOMNESS: R', S', T' must be uniform, fresh and secret.  Reused or predictable values make the output linkable to
+ * its input.
+ * INPUTS: rerandomized proofs usually arrive from another party.  Points outside the prime-order subgroups give
+ * UNDEFINED results, exactly as on the other compute entry points (see the top of this file): decode them with
+ * gs_wire_decode_* (validate = 1), run them through gs_validate_points[_dev], or set gs_set_option("endo", 0).
+ * Outputs must not overlap any input or each other: the host form returns GS_ERR_ARG if they do; for the _dev form it
+ * is the caller's contract (results are undefined otherwise).  Shapes and errors as gs_prove_batch; N = 0 is a no-op. */
+int gs_rerandomize_batch_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                             const void* Gamma, const void* xcoms, const void* ycoms, const void* pi,
+                             const void* theta, const void* R, const void* S, const void* T, void* xcoms_out,
+                             void* ycoms_out, void* pi_out, void* theta_out);
+int gs_rerandomize_batch(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                         const void* Gamma, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                         const void* R, const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
+                         void* theta_out);
+/* A Statement (gs_prove_statement's shape): xcoms[m], ycoms[n], R'[m][kx], S'[n][ky] (and xcoms_out / ycoms_out) are
+ * ONE shared copy, updated once; A, B, Gamma, pi, theta and T'[E][ky][kx] are per equation.  The output equals
+ * gs_prove_statement(X, Y, R + R', S + S', T_e + T'_e + S'^T Gamma_e^T R) for every equation e. */
+int gs_rerandomize_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B,
+                                 const void* Gamma, const void* xcoms, const void* ycoms, const void* pi,
+                                 const void* theta, const void* R, const void* S, const void* T, void* xcoms_out,
+                                 void* ycoms_out, void* pi_out, void* theta_out);
+int gs_rerandomize_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B,
+                             const void* Gamma, const void* xcoms, const void* ycoms, const void* pi,
+                             const void* theta, const void* R, const void* S, const void* T, void* xcoms_out,
+                             void* ycoms_out, void* pi_out, void* theta_out);
 
 /* ---- verify (src/verifier.rs) ------------------------------------------- */
 /* ok[i] = 1 iff equation i verifies; exact reference semantics (four GT cell

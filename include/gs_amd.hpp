@@ -191,6 +191,52 @@ CommitT<Com> batch_commit(const std::vector<V>& vars, const CRS& key, Rng& rng, 
   c.coms = split<Com>(out, vars.size());
   return c;
 }
+// a + b mod r on Montgomery limbs (the Montgomery map is additive); r of BLS12-381 / BN254, little-endian u64 limbs
+inline Fr fr_add(const Fr& a, const Fr& b, int curve) {
+  static const uint64_t R[2][4] = {{0xffffffff00000001ull, 0x53bda402fffe5bfeull, 0x3339d80809a1d805ull, 0x73eda753299d7d48ull},
+                                   {0x43e1f593f0000001ull, 0x2833e84879b97091ull, 0xb85045b68181585dull, 0x30644e72e131a029ull}};
+  if (a.v.size() != 32 || b.v.size() != 32) throw Panic("assertion failed: Fr is 32 bytes");
+  const uint64_t* r = R[curve == GS_CURVE_BN254 ? 1 : 0];
+  uint64_t x[4], y[4], s[4], d[4];
+  memcpy(x, a.v.data(), 32);
+  memcpy(y, b.v.data(), 32);
+  unsigned __int128 c = 0;
+  for (int i = 0; i < 4; i++) {  // both < r < 2^255: no carry out of the top limb
+    c += (unsigned __int128)x[i] + y[i];
+    s[i] = (uint64_t)c;
+    c >>= 64;
+  }
+  uint64_t br = 0;
+  for (int i = 0; i < 4; i++) {
+    unsigned __int128 t = (unsigned __int128)s[i] - r[i] - br;
+    d[i] = (uint64_t)t;
+    br = (uint64_t)(t >> 64) & 1;
+  }
+  Fr o;
+  o.v.resize(32);
+  memcpy(o.v.data(), br ? s : d, 32);
+  return o;
+}
+inline Matrix<Fr> fr_mat_add(const Matrix<Fr>& a, const Matrix<Fr>& b, int curve) {
+  assert_eq(a.size(), b.size(), "matrix rows");
+  Matrix<Fr> o(a.size());
+  for (size_t i = 0; i < a.size(); i++) {
+    assert_eq(a[i].size(), b[i].size(), "matrix columns");
+    for (size_t j = 0; j < a[i].size(); j++) o[i].push_back(fr_add(a[i][j], b[i][j], curve));
+  }
+  return o;
+}
+// Matrix<Fr> product on the engine (gs_fr_matmul)
+inline Matrix<Fr> fr_matmul(const Ctx& cx, const Matrix<Fr>& a, const Matrix<Fr>& b) {
+  size_t rows = a.size(), inner = b.size(), cols = inner ? b[0].size() : 0;
+  for (const auto& r : a) assert_eq(r.size(), inner, "lhs columns");
+  Bytes x = cat(a), y = cat(b), o(rows * cols * 32);
+  cx.chk(gs_fr_matmul(cx.c, (int)rows, (int)inner, (int)cols, x.data(), y.data(), o.data()));
+  Matrix<Fr> out(rows);
+  for (size_t i = 0; i < rows; i++)
+    for (size_t j = 0; j < cols; j++) out[i].push_back(Fr{Bytes(o.begin() + (i * cols + j) * 32, o.begin() + (i * cols + j + 1) * 32)});
+  return out;
+}
 }  // namespace detail
 
 // commit.rs:78-100, 178-200, 125-156, 225-256 (+ the single-element forms :59-75, 103-122, 159-175, 203-222)
@@ -335,6 +381,54 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     cx.chk(gs_verify_batch(cx.c, (int)TYPE, 1, (int)m, (int)n, A.data(), B.data(), G.data(), target.v.data(),
                            xc.data(), yc.data(), pi.data(), th.data(), &ok));
     return ok == 1;
+  }
+
+  // (new) A fresh-looking CProof from `com_proof` alone, no witness (gs_rerandomize_batch).  Draws R' (m x KX), then
+  // S' (n x KY), then T' (KY x KX) -- the reference's order; they must be uniform, fresh and secret.  When the input
+  // carries its randomness, the result carries R + R', S + S' and T + T' + S'^T Gamma^T R: exactly the CProof that
+  // commit_and_prove with that randomness would have produced.  Proofs from another party should be decoded with
+  // validation first (gs_amd.h, gs_rerandomize_batch).
+  template <class Rng> CProof rerandomize(const CProof& com_proof, const CRS& crs, Rng& rng) const {
+    assert_eq(com_proof.equ_proofs.size(), 1, "com_proof.equ_proofs.len() == 1");
+    if (com_proof.equ_proofs[0].equ_type != TYPE) throw Panic("assertion failed: equation type matches the proof's");
+    const EquProof& pf = com_proof.equ_proofs[0];
+    size_t m = com_proof.xcoms.coms.size(), n = com_proof.ycoms.coms.size();
+    if (m == 0 || n == 0) throw Panic("index out of bounds: empty commitment list");
+    check_statement_shape(m, n);
+    assert_eq(pf.pi.size(), KX, "pi.len()");
+    assert_eq(pf.theta.size(), KY, "theta.len()");
+    Matrix<Fr> R1 = detail::draw(rng, m, KX), S1 = detail::draw(rng, n, KY), T1 = detail::draw(rng, KY, KX);
+    const Ctx& cx = *crs.ctx;
+    const size_t sx = is_scalar<A1>::value ? cx.sz[1] : cx.sz[2], sy = is_scalar<A2>::value ? cx.sz[1] : cx.sz[3];
+    Bytes A = cat(a_consts), B = cat(b_consts), G = cat(gamma), xc = cat(com_proof.xcoms.coms),
+          yc = cat(com_proof.ycoms.coms), pi = cat(pf.pi), th = cat(pf.theta), R = cat(R1), S = cat(S1), T = cat(T1);
+    assert_eq(A.size(), n * sx, "a_consts bytes");
+    assert_eq(B.size(), m * sy, "b_consts bytes");
+    assert_eq(G.size(), m * n * cx.sz[1], "gamma bytes");
+    assert_eq(xc.size(), m * 2 * cx.sz[2], "xcoms bytes");
+    assert_eq(yc.size(), n * 2 * cx.sz[3], "ycoms bytes");
+    assert_eq(pi.size(), KX * 2 * cx.sz[3], "pi bytes");
+    assert_eq(th.size(), KY * 2 * cx.sz[2], "theta bytes");
+    Bytes xo(xc.size()), yo(yc.size()), po(pi.size()), to(th.size());
+    cx.chk(gs_rerandomize_batch(cx.c, (int)TYPE, 1, (int)m, (int)n, A.data(), B.data(), G.data(), xc.data(), yc.data(),
+                                pi.data(), th.data(), R.data(), S.data(), T.data(), xo.data(), yo.data(), po.data(),
+                                to.data()));
+    CProof out{{split<Com1>(xo, m), {}}, {split<Com2>(yo, n), {}}, {}};
+    EquProof np{split<Com2>(po, KX), split<Com1>(to, KY), TYPE, {}};
+    if (com_proof.xcoms.rand.size() == m && com_proof.ycoms.rand.size() == n && pf.rand.size() == KY) {
+      out.xcoms.rand = detail::fr_mat_add(com_proof.xcoms.rand, R1, cx.curve_id);
+      out.ycoms.rand = detail::fr_mat_add(com_proof.ycoms.rand, S1, cx.curve_id);
+      // T'' = T + T' + (S'^T Gamma^T) R, the products on the prover's own kernels (gs_fr_matmul)
+      Matrix<Fr> St(KY, std::vector<Fr>(n)), Gt(n, std::vector<Fr>(m));
+      for (size_t j = 0; j < n; j++)
+        for (size_t l = 0; l < KY; l++) St[l][j] = S1[j][l];
+      for (size_t i = 0; i < m; i++)
+        for (size_t j = 0; j < n; j++) Gt[j][i] = gamma[i][j];
+      Matrix<Fr> cross = detail::fr_matmul(cx, detail::fr_matmul(cx, St, Gt), com_proof.xcoms.rand);
+      np.rand = detail::fr_mat_add(detail::fr_mat_add(pf.rand, T1, cx.curve_id), cross, cx.curve_id);
+    }
+    out.equ_proofs.push_back(np);
+    return out;
   }
 };
 
