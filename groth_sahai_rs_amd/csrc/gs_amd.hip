@@ -2210,7 +2210,7 @@ template <class C> struct Impl {
     RC(scratch(c, "rlc.s1", N * n1 * Z::COM1, &s1));
     {
       SidePlan sp;
-      sp.tm = 4;
+      sp.tm = c->endo ? 4 : 1;  // endo = 0: one plain double-and-add lane per term ("k_var.plain"), as everywhere else
       int slot = 0;
       for (int q = 0; q < n1; q++) {
         int arr = q < m ? 0 : 1, idx = q < m ? q : q - m;
@@ -2243,7 +2243,7 @@ template <class C> struct Impl {
     RC(scratch(c, "rlc.s2", N * n2 * Z::COM1, &s2));
     {
       SidePlan sp;
-      sp.tm = 8;
+      sp.tm = c->endo ? 8 : 1;
       int slot = 0;
       for (int q = 0; q < n2; q++) {
         int b0 = slot, e0 = 0, b1 = 0;

@@ -97,7 +97,10 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  *                   defined on ANY curve point, like the reference's Com::scalar_mul (data_structures.rs:336-342), at
  *                   ~2.5x the variable-base work.  For callers that cannot vouch for subgroup membership and do not want
  *                   to pay gs_validate_points first.  (This one changes WHICH inputs are supported, not the results on
- *                   supported ones.)
+ *                   supported ones.)  The batched verifier gs_verify_batch_rlc[_dev] and the shards of
+ *                   gs_multi_verify_batch_rlc[_dev] follow it too: with 0 the rho-weighted G1 combinations of both of
+ *                   its passes run as one "k_var.plain" lane per term (no "k_var_multi*" Straus groups), and the
+ *                   accumulator pair and the verdict are those of endo = 1.
  *   "mixed_merge"  -1 planned (merged up to 2^14 equations per call on a 256-CU device) | 0 the parts of a mixed call run
  *                   one after the other | 1 their launches are merged
  * The same knobs are read ONCE at gs_ctx_create from the environment for experiments without recompiling the caller:

@@ -770,7 +770,7 @@ static void prove(int ty, int m, int n, const void* X, const void* Y, const void
 
 /* ---------------------------------------------------------- verify ------- */
 static int verify(int ty, int m, int n, const void* A, const void* B, const fr* G, const void* target,
-                  const com1* xc, const com2* yc, const com2* pi, const com1* theta, const crs_t* k) {
+                  const com1* xc, const com2* yc, const com2* pi, const com1* theta, const crs_t* k, comt* cells) {
   int kx = xg(ty) ? 2 : 1, ky = yg(ty) ? 2 : 1;
   com1* ma = (com1*)malloc(sizeof(com1) * n);
   com2* mb = (com2*)malloc(sizeof(com2) * m);
@@ -800,6 +800,8 @@ static int verify(int ty, int m, int n, const void* A, const void* B, const fr* 
   comt_add(&t, &lin_t, &com1_pf2); comt_add(&rhs, &t, &pf1_com2);
   int ok = 1;
   for (int i = 0; i < 4; i++) ok &= f12_eq(&lhs.c[i], &rhs.c[i]);
+  /* the compared values themselves (ref_verify_cells): lhs, rhs, and rhs without lin_t */
+  if (cells) { cells[0] = lhs; cells[1] = rhs; comt_add(&cells[2], &com1_pf2, &pf1_com2); }
   free(ma); free(mb); free(stmt_com_y);
   return ok;
 }
@@ -832,8 +834,20 @@ void ref_commit_and_prove(int ty, int m, int n, const void* X, const void* Y, co
 int ref_verify(int ty, int m, int n, const void* A, const void* B, const void* G, const void* target, const void* xc,
                const void* yc, const void* pi, const void* theta, const void* crs) {
   return verify(ty, m, n, A, B, (const fr*)G, target, (const com1*)xc, (const com2*)yc, (const com2*)pi,
-                (const com1*)theta, (const crs_t*)crs);
+                (const com1*)theta, (const crs_t*)crs, NULL);
 }
+/* verify() with its operands: cells = 12 GT in ComT cell order (0,0) (0,1) (1,0) (1,1): the four lhs, the four rhs, the
+ * four rhs without the target's lin_t.  Returns the verdict (lhs == rhs in all four cells). */
+int ref_verify_cells(int ty, int m, int n, const void* A, const void* B, const void* G, const void* target,
+                     const void* xc, const void* yc, const void* pi, const void* theta, const void* crs, void* cells) {
+  return verify(ty, m, n, A, B, (const fr*)G, target, (const com1*)xc, (const com2*)yc, (const com2*)pi,
+                (const com1*)theta, (const crs_t*)crs, (comt*)cells);
+}
+/* group and GT arithmetic for the forged-proof builder of the tests (tests/forge.py) */
+void ref_g1_add(const void* p, const void* q, void* out) { g1_add((g1a*)out, (const g1a*)p, (const g1a*)q); }
+void ref_g2_add(const void* p, const void* q, void* out) { g2_add((g2a*)out, (const g2a*)p, (const g2a*)q); }
+void ref_gt_mul(const void* a, const void* b, void* out) { f12_mul((fp12*)out, (const fp12*)a, (const fp12*)b); }
+void ref_gt_inv(const void* a, void* out) { f12_inv((fp12*)out, (const fp12*)a); }
 /* Matrix<Fr>::right_mul (data_structures.rs:824-869): out (ar x bc) = a (ar x ac) * b (ac x bc), Montgomery Fr */
 void ref_fr_matmul(int ar, int ac, int bc, const void* a, const void* b, void* out) { fr_matmul((fr*)out, (const fr*)a, ar, ac, (const fr*)b, bc); }
 u64 ref_fpmul_count(int reset) { u64 v = g_fpmul_count; if (reset) g_fpmul_count = 0; return v; }
@@ -878,7 +892,7 @@ static void* bench_worker(void* arg) {
                          b->R + e * m * 2, b->S + e * n * 2, b->T + e * 4, &b->crs, b->xc + e * m, b->yc + e * n,
                          b->pi + e * 2, b->th + e * 2);
     b->ok[e] = verify(PPE, m, n, b->A + e * n, b->B + e * m, b->G + e * m * n, &b->target[e], b->xc + e * m,
-                      b->yc + e * n, b->pi + e * 2, b->th + e * 2, &b->crs);
+                      b->yc + e * n, b->pi + e * 2, b->th + e * 2, &b->crs, NULL);
   }
   pthread_mutex_lock(&b->mu);
   b->fpmuls += g_fpmul_count;

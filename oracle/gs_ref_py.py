@@ -98,3 +98,38 @@ def fr_matmul(curve, ar, ac, bc, a, b):
     out = np.zeros(ar * bc * 32, np.uint8)
     lib(curve).ref_fr_matmul(ar, ac, bc, _p(_u8(a)), _p(_u8(b)), _p(out))
     return out
+
+
+def verify_cells(curve, ty, m, n, A, B, G, target, xc, yc, pi, theta, crs):
+    """(verdict, lhs[4], rhs[4], rhs without lin_t [4]): the GT values verify() compares, cells (0,0) (0,1) (1,0) (1,1)"""
+    GT = sizes(curve)[4]
+    cells = np.zeros(12 * GT, np.uint8)
+    ok = int(lib(curve).ref_verify_cells(ty, m, n, _p(_u8(A)), _p(_u8(B)), _p(_u8(G)), _p(_u8(target)), _p(_u8(xc)),
+                                         _p(_u8(yc)), _p(_u8(pi)), _p(_u8(theta)), _p(_u8(crs)), _p(cells)))
+    c = cells.reshape(3, 4, GT)
+    return ok, c[0], c[1], c[2]
+
+
+def g_add(curve, group, p, q):
+    FQ, FR, G1, G2, GT, CRS = sizes(curve)
+    out = np.zeros(G1 if group == 1 else G2, np.uint8)
+    (lib(curve).ref_g1_add if group == 1 else lib(curve).ref_g2_add)(_p(_u8(p)), _p(_u8(q)), _p(out))
+    return out
+
+
+def gt_mul(curve, a, b):
+    out = np.zeros(sizes(curve)[4], np.uint8)
+    lib(curve).ref_gt_mul(_p(_u8(a)), _p(_u8(b)), _p(out))
+    return out
+
+
+def gt_inv(curve, a):
+    out = np.zeros(sizes(curve)[4], np.uint8)
+    lib(curve).ref_gt_inv(_p(_u8(a)), _p(out))
+    return out
+
+
+def gt_pow(curve, base, k_mont):
+    out = np.zeros(sizes(curve)[4], np.uint8)
+    lib(curve).ref_gt_pow(_p(_u8(base)), _p(_u8(k_mont)), _p(out))
+    return out
