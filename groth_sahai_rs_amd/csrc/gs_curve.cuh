@@ -80,6 +80,7 @@ template <class F> GS_JAC void jac_madd(Jac<F>& r, const Jac<F>& p, const Aff<F>
   F u2 = mul(q.x, z1z1);
   F s2 = mul(mul(q.y, p.z), z1z1);
   F h = norm(sub(u2, p.x));
+  zero_window_check(h);  // (CPU twin: |k| of H inside the generated filter's window; nothing on the device)
   F rr = sub(s2, p.y);
   if (is_zero(h)) {
     if (is_zero(rr)) {
@@ -116,6 +117,7 @@ template <class F> GS_JAC void jac_add(Jac<F>& r, const Jac<F>& p, const Jac<F>&
   F u1 = mul(p.x, z2z2), u2 = mul(q.x, z1z1);
   F s1 = mul(mul(p.y, q.z), z2z2), s2 = mul(mul(q.y, p.z), z1z1);
   F h = norm(sub(u2, u1));
+  zero_window_check(h);  // (CPU twin: |k| of H inside the generated filter's window; nothing on the device)
   F rr = sub(s2, s1);
   if (is_zero(h)) {
     if (is_zero(rr)) {

@@ -12,7 +12,11 @@
 // Representation: element a is held as the integer  V = a * 2^(28 L) mod p, lazily
 // reduced: V may be any representative with |V| < 2^(28L-6), limbs are int32 with
 // V = sum v[i] 2^(28 i).  "Normalised" means v[0..L-2] in [0, 2^28 + small) and the
-// top limb signed.  mul() returns normalised limbs and a value in (-p/2, 3p/2).
+// top limb signed.  mul(a, b) returns normalised limbs (0..L-2 in [0, 2^28)) and the value (V_a V_b + m p) / 2^(28L)
+// with 0 <= m < 2^(28L): it lies in [V_a V_b / 2^(28L), V_a V_b / 2^(28L) + p), i.e. in (-p/2, 3p/2) whenever
+// |V_a V_b| < 2^(28L) p/2 -- every product of values that are themselves products or short lazy sums of products.  (Two
+// operands at the value limit 2^(28L-6) give up to +-0.62 p on BLS12-381 and +-2^14.4 p on BN254, whose p has 26 bits
+// less than 2^(28L): the interval is a property of the operands' values, not of the limb contract.)
 // Contract for mul(a, b): 14 * max|a_i| * max|b_j| + 14 * 2^56 < 2^63, i.e. the
 // limb-growth factors satisfy A*B <= 8 (a sum of two normalised values has A = 2);
 // callers call norm() where a longer sum feeds a product.  With GS_FQ28_CHECK
@@ -151,7 +155,11 @@ template <class C> GS_HD Fq28<C> norm_full(const Fq28<C>& a) {
 // value reduction: subtract round(V/p) * p (quotient estimated in f32 from the two top
 // limbs).  Needed only where a value is fed back LINEARLY (cyclotomic squaring:
 // z <- 3t - 2z doubles |V| per step); everywhere else multiplication contracts values.
-// Input: weakly normalised limbs, |V| < 2^20 p.  Output: unique limbs, |V| <= ~p.
+// Input: weakly normalised limbs, |V| < 2^20 p.  Output: unique limbs (0..L-2 in [0, 2^28)) of V - k p with
+//   |V - k p| < (1/2 + 2^-21 |V| / p) p + 2^(28(L-2)+1),   hence   < p + 2^(28(L-2)+1)   over the whole input range
+// (the CPU twin asserts the latter on the two top limbs).  k is the rounding of a quotient that carries four f32 roundings
+// (the two limb conversions or their sum, the constant, the product: relative error < 4 2^-24 = 2^-22 of |V| / p; the
+// bound is stated with 2^-21, a factor two to spare) and ignores the limbs below the two top ones (the last term).
 template <class C> GS_HD Fq28<C> vreduce(const Fq28<C>& a) {
   constexpr int L = C::L;
   float v = (float)a.v[L - 1] * 268435456.0f + (float)a.v[L - 2];
@@ -165,6 +173,15 @@ template <class C> GS_HD Fq28<C> vreduce(const Fq28<C>& a) {
     acc >>= 28;
   }
   r.v[L - 1] = (limb_t)((int64_t)a.v[L - 1] - (int64_t)k * C::P28[L - 1] + acc);
+#if defined(GS_FQ28_CHECK)
+  {
+    const int64_t top2 = (int64_t)r.v[L - 1] * 268435456 + r.v[L - 2], ptop2 = (int64_t)C::P28[L - 1] * 268435456 + C::P28[L - 2];
+    if (top2 > ptop2 + 1 || top2 < -ptop2 - 2) {
+      fprintf(stderr, "vreduce: |V - k p| >= p (input outside |V| < 2^20 p?)\n");
+      abort();
+    }
+  }
+#endif
   return r;
 }
 
@@ -599,18 +616,43 @@ template <class C> constexpr uint64_t pinv56() {
   for (int i = 0; i < 6; i++) x *= 2 - p * x;
   return x & (((uint64_t)1 << 56) - 1);
 }
-// the cheap "cannot be 0 mod p" filter on its own: false = certainly not a multiple of p.  V = k p with |k| < 2^20
-// (every lazily reduced value within the mul contract) forces (V mod 2^56) p^-1 mod 2^56 to be the small signed integer
-// k.  Only limbs 0 and 1 enter (V mod 2^56 needs no carry propagation), and a non-multiple passes with probability
-// 2^-35.  (Rounds 1-3 filtered on 28 bits of the fully carried value: a non-multiple passed with probability 2^-7 PER
+// the cheap "cannot be 0 mod p" filter on its own: false = certainly not a multiple of p.  V = k p with |k| <= 2^25
+// forces (V mod 2^56) p^-1 mod 2^56 to be the small signed integer k.  The window covers every value is_zero_slow
+// accepts: any int32 limbs whose norm() has |top limb| < 2^26 (what the multiplier inside it asserts), i.e.
+// |V| < 2^(28L-2), which is |k| < 2^9.3 on BLS12-381 and |k| < 2^24.4 on BN254 (p of 254 bits under 2^280).  (The window
+// was 2^20 until the contract tests: short of BN254's value contract 2^(28L-6) = 2^20.4 p already.  Nothing the
+// engine hands to is_zero comes near either -- differences of coordinates and of products, |k| of a few units -- so
+// results are unchanged; the generated point additions keep their own 2^20 window for H = U2 - X of such values.)
+// Only limbs 0 and 1 enter (V mod 2^56 needs no carry propagation), and a non-multiple passes with probability
+// 2^-30.  (Rounds 1-3 filtered on 28 bits of the fully carried value: a non-multiple passed with probability 2^-7 PER
 // LANE, i.e. in 39 % of the waves, and every point addition asks this about its H.)
 template <class C> GS_HD bool maybe_zero_limbs01(limb_t v0, limb_t v1) {
   const uint64_t m56 = ((uint64_t)1 << 56) - 1;
   uint64_t V = (uint64_t)(int64_t)v0 + ((uint64_t)(int64_t)v1 << 28);
   uint64_t k = (V * pinv56<C>()) & m56;
   int64_t ks = (int64_t)(k << 8) >> 8;  // sign-extend 56 bits
-  return !(ks > ((int64_t)1 << 20) || ks < -((int64_t)1 << 20));
+  return !(ks > ((int64_t)1 << 25) || ks < -((int64_t)1 << 25));
 }
+// CPU twin only: what is handed to a zero test stays inside the SMALLEST window in use.  The generated point additions
+// (gen_pointops_asm.py) filter their H = U2 - X with |k| <= 2^20, narrower than is_zero's; the formulas of gs_curve.cuh
+// call this on the same H, so that "H has |k| of a few units" is asserted on every addition the twin runs and not only
+// argued: |V| < 2^20 p, on the two top limbs of the fully carried value.
+template <class C> GS_HD void zero_window_check(const Fq28<C>& a) {
+#if defined(GS_FQ28_CHECK)
+  constexpr int L = C::L;
+  const Fq28<C> n = norm_full(a);
+  __int128 top2 = (__int128)n.v[L - 1] * 268435456 + n.v[L - 2];
+  const __int128 lim = ((__int128)C::P28[L - 1] * 268435456 + C::P28[L - 2]) << 20;
+  if (top2 < 0) top2 = -top2;
+  if (top2 >= lim) {
+    fprintf(stderr, "zero test: |V| >= 2^20 p, outside the window of the generated point additions' H = 0 filter\n");
+    abort();
+  }
+#else
+  (void)a;
+#endif
+}
+// a == 0 (mod p) for any int32 limbs whose norm() has |top limb| < 2^26 (is_zero_slow's range; the filter's window covers it)
 template <class C> GS_HD bool is_zero(const Fq28<C>& a) {
   if (!maybe_zero_limbs01<C>(a.v[0], a.v[1])) return false;
   return is_zero_slow(a);  // the robust test decides

@@ -57,6 +57,10 @@ template <class C> GS_HD Fp2<C> mul_small(const Fp2<C>& a, int k) { return {mul_
 template <class C> GS_HD bool is_zero(const Fp2<C>& a) { return is_zero(a.c0) && is_zero(a.c1); }
 template <class C> GS_HD bool is_zero_limbs(const Fp2<C>& a) { return is_zero_limbs(a.c0) && is_zero_limbs(a.c1); }
 template <class C> GS_HD bool eq(const Fp2<C>& a, const Fp2<C>& b) { return is_zero(sub(a, b)); }
+template <class C> GS_HD void zero_window_check(const Fp2<C>& a) {
+  zero_window_check(a.c0);
+  zero_window_check(a.c1);
+}
 template <class C> GS_HD Fp2<C> select(bool c, const Fp2<C>& a, const Fp2<C>& b) {
   return {select(c, a.c0, b.c0), select(c, a.c1, b.c1)};
 }

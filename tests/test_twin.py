@@ -7,6 +7,7 @@ test_gpu_parity.py."""
 import ctypes
 import os
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -24,7 +25,7 @@ def twin():
         os.path.join(REPO, "groth_sahai_rs_amd", "csrc", f)
         for f in os.listdir(os.path.join(REPO, "groth_sahai_rs_amd", "csrc"))
         if f.endswith((".cuh", ".h"))
-    ]
+    ] + [os.path.join(HERE, "hip", "arith_ops.inc")]
     if not os.path.exists(TWIN_SO) or any(os.path.getmtime(s) > os.path.getmtime(TWIN_SO) for s in srcs):
         if not os.path.exists(CLANG):
             pytest.skip("no host clang++ for the CPU twin")
@@ -274,3 +275,26 @@ def test_fixed_argument_line_tables(twin, cname):
         f(n3, ptr(P3), ptr(Q3), mask, ptr(a), 1)
         f(n3, ptr(P3), ptr(Q3), mask, ptr(b), 2)
         assert (a == b).all(), mask
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_raw_limb_operations_at_contract_limits(twin, cname, tmp_path):
+    """The operation table of tests/hip/arith_ops.inc -- base field, Fp2, tower, curve -- on the adversarial RAW limb
+    vectors of tests/arithvec.py (column extremes of every multiplier, N inputs with every limb at the edge of its range and
+    the top limb at the value-contract limit, multiples of p up to the limit of is_zero, vreduce next to half-integer
+    quotients, lazy representatives for the inversion, all three branches of fq_to_boundary), through twin_raw_op_<curve>.
+    Built with -DGS_FQ28_CHECK the twin asserts every INTERNAL contract on the way (each Karatsuba sum, each lazy chain, each
+    column accumulator), which is where a missing norm() shows; the results are compared with big integers.  The calls run
+    in a child process: an abort() from a contract assertion is a failure carrying its message, not the death of pytest --
+    and on an in-contract input it is a finding, not a test problem."""
+    import numpy as np
+
+    import arithvec as av
+
+    out = str(tmp_path / "raw.npz")
+    r = subprocess.run([sys.executable, os.path.join(HERE, "arithvec.py"), TWIN_SO, "twin_raw_op_" + cname, cname, out,
+                        ",".join(av.OPS)], capture_output=True, text=True, cwd=HERE)
+    assert r.returncode == 0, "the twin's raw operations ended with status %d:\n%s" % (r.returncode, r.stderr[-2000:])
+    res = np.load(out)
+    for op in av.OPS:
+        av.check_all(cname, op, av.op_cases(cname, op), res[op])

@@ -21,6 +21,22 @@ GS_ZERO_ONE(Bls12_381)
 GS_ZERO_ONE(Bn254)
 }
 using namespace gs;
+#include "../hip/arith_ops.inc"
+
+// Raw-limb entry: the operation table of tests/hip/arith_ops.inc on operand limb vectors as they are (no boundary
+// conversion), item by item -- the same dispatch the device probe runs, here with every contract assertion of the headers
+// on.  A contract violation aborts the process: the caller runs this in a child process.
+template <class C> static int raw_op(int op, int n, const int32_t* in, int32_t* out) {
+  if (op < 0 || op >= arith::NUM_OPS) return -1;
+  const size_t sin = (size_t)arith::op_nin(op) * C::L, sout = (size_t)arith::op_nout(op) * C::L;
+  for (int i = 0; i < n; i++) switch (op) {
+#define ARITH_CASE(K) \
+  case K: arith::arith_op<C, K>(in + i * sin, out + i * sout); break;
+      ARITH_FOR_EACH_OP(ARITH_CASE)
+#undef ARITH_CASE
+    }
+  return 0;
+}
 
 // The 3-lane cooperative exponentiation (gs_coop.cuh) on three host threads: the exchange policy is a
 // mailbox with a barrier where the device uses wave shuffles; the lane code is the device's.
@@ -479,6 +495,7 @@ extern "C" long twin_fq_mul_count(int reset) {
   extern "C" {                                                                                                    \
   void twin_fp_mul_##SUF(const uint8_t* a, const uint8_t* b, uint8_t* o) { Twin<CURVE>::fp_mul(a, b, o); }       \
   void twin_fp_inv_##SUF(const uint8_t* a, uint8_t* o) { Twin<CURVE>::fp_inv(a, o); }                            \
+  int twin_raw_op_##SUF(int op, int n, const int32_t* in, int32_t* out) { return raw_op<CURVE>(op, n, in, out); }  \
   void twin_fp_addsub_##SUF(const uint8_t* a, const uint8_t* b, uint8_t* o) { Twin<CURVE>::fp_addsub(a, b, o); } \
   int twin_fp_is_zero_##SUF(const uint8_t* a, const uint8_t* b) { return Twin<CURVE>::fp_is_zero(a, b); }        \
   void twin_fr_mul_##SUF(const uint32_t* a, const uint32_t* b, uint32_t* o) { Twin<CURVE>::fr_mul(a, b, o); }    \
