@@ -566,11 +566,17 @@ struct MCost {
 #ifndef GS_PLAN_PAIR
 #define GS_PLAN_PAIR 1
 #endif
-// (profiles/r3/fq_mul_counts.json: miller*_per_lane, _per_pair / _per_triple, _per_fixed_pair / _per_fixed_triple --
-// the counts of the unpaired line products both curves use since round 3)
+// (profiles/r5/fq_mul_counts.json: miller*_per_lane, _per_pair / _per_triple, _per_fixed_pair / _per_fixed_triple --
+// the counts with real-form lines: stepped lines of the twin forms and every tabulated line go through the 72 L^2
+// sparse product; -DGS_LINES_GENERAL has the round-3 counts of the general product)
 static inline MCost mcost(int curve, bool twin) {
+#if defined(GS_LINES_GENERAL)
   if (curve == 0) return twin ? MCost{4536.0, 7764.0, 6256.0} : MCost{2268.0, 4636.0, 3128.0};
   return twin ? MCost{4680.0, 10519.0, 8096.0} : MCost{2340.0, 6471.0, 4048.0};
+#else
+  if (curve == 0) return twin ? MCost{4536.0, 7356.0, 5304.0} : MCost{2268.0, 4636.0, 2652.0};
+  return twin ? MCost{4680.0, 9991.0, 6864.0} : MCost{2340.0, 6471.0, 3432.0};
+#endif
 }
 static inline bool pair_fixed(bool lt, const PairRef& r) { return lt && r.q_arr == 2; }  // Q array 2 = CRS (v, W2)
 // Split one cell's pairs into the fewest tasks whose lane cost stays within `budget`: costly pairs first, each to the

@@ -219,7 +219,7 @@ inline std::atomic<long>& fq28_mul_counter() {
   return n;
 }
 // ... and the multiply-add instructions the DEVICE kernels execute for them (static counts of gs_mul28_asm.h: product
-// 2 L^2, squaring L (L + 1) / 2 + L^2, Fp2 product 6 L^2, Fp2 squaring 4 L^2, three-term Fp2 dot product 14 L^2): the
+// 2 L^2, squaring L (L + 1) / 2 + L^2, Fp2 product 6 L^2, Fp2 squaring 4 L^2, three-term Fp2 dot product 14 L^2, 12 L^2 with a real last operand): the
 // "executed" side of bench.py's ALU accounting, where the counter above credits a squaring as a full product
 inline std::atomic<long>& fq28_mad_counter() {
   static std::atomic<long> n{0};
@@ -508,6 +508,96 @@ GS_HD void fp2dot3_28(Fq28<C>& r0, Fq28<C>& r1, const Fq28<C>& a00, const Fq28<C
   const int32_t* a[6] = {a00.v, a01.v, a10.v, a11.v, a20.v, a21.v};
   const int32_t* b[6] = {b00.v, b01.v, b10.v, b11.v, b20.v, b21.v};
   fp2dot3_28_generic<C, int32_t>(r0.v, r1.v, a, b);
+#endif
+}
+
+// ---- the same with a REAL last right-hand operand: c = a0 b0 + a1 b1 + a2 r, r in Fq --------------------------------
+// (gs_mul28_asm.h, "the last right-hand operand real").  c0 += a20 r, c1 += a21 r: two limb products where a general
+// b2 needs four, 12 L^2 multiply-adds instead of 14 L^2.  The Miller lines scaled to a real y coefficient
+// (gs_pairing.cuh) go into the accumulator through six of these (f12_mul_by_014r / _034r, gs_tower.cuh).  Contract, from
+// the column count (2 L products per full pair, L for the real one, L reduction terms, a signed 64-bit accumulator):
+//   2 (A_a0 A_b0 + A_a1 A_b1) + A_a2 A_r <= 8;
+// the dot product's own sum_t A_at A_bt <= 4 is sufficient.  The CPU twin asserts the columns.  a: three (re, im); b: two.
+template <class C, class T>
+GS_HD void fp2dot3r_28_generic(T* r0, T* r1, const T* const* a, const T* const* b, const T* rr) {
+  constexpr int L = C::L;
+  uint32_t m0[L], m1[L];
+#if defined(GS_FQ28_CHECK)
+  __int128 acc0 = 0, acc1 = 0;
+#else
+  int64_t acc0 = 0, acc1 = 0;
+#endif
+#pragma unroll
+  for (int k = 0; k < 2 * L - 1; k++) {
+#pragma unroll
+    for (int i = 0; i < L; i++) {
+      int j = k - i;
+      if (j < 0 || j >= L) continue;
+#pragma unroll
+      for (int t = 0; t < 2; t++) {
+        acc0 += (int64_t)a[2 * t][i] * b[2 * t][j] - (int64_t)a[2 * t + 1][i] * b[2 * t + 1][j];
+        acc1 += (int64_t)a[2 * t][i] * b[2 * t + 1][j] + (int64_t)a[2 * t + 1][i] * b[2 * t][j];
+      }
+      acc0 += (int64_t)a[4][i] * rr[j];
+      acc1 += (int64_t)a[5][i] * rr[j];
+      if (j >= 1 && i < k) {
+        acc0 += (int64_t)(int32_t)m0[i] * C::P28[j];
+        acc1 += (int64_t)(int32_t)m1[i] * C::P28[j];
+      }
+    }
+#if defined(GS_FQ28_CHECK)
+    {
+      const __int128 lim = (__int128)1 << 63;
+      if (acc0 >= lim || acc0 < -lim || acc1 >= lim || acc1 < -lim) {
+        fprintf(stderr, "Fp2 dot product (real operand): column accumulator leaves the signed 64-bit range\n");
+        abort();
+      }
+    }
+#endif
+    if (k < L) {
+      m0[k] = ((((uint32_t)acc0) & (uint32_t)M28) * C::P28_INV) & (uint32_t)M28;
+      m1[k] = ((((uint32_t)acc1) & (uint32_t)M28) * C::P28_INV) & (uint32_t)M28;
+      acc0 += (int64_t)(int32_t)m0[k] * C::P28[0];
+      acc1 += (int64_t)(int32_t)m1[k] * C::P28[0];
+    } else {
+      r0[k - L] = (T)(((uint32_t)acc0) & (uint32_t)M28);
+      r1[k - L] = (T)(((uint32_t)acc1) & (uint32_t)M28);
+    }
+    acc0 >>= 28;
+    acc1 >>= 28;
+  }
+  r0[L - 1] = (T)acc0;
+  r1[L - 1] = (T)acc1;
+}
+// r = a0 b0 + a1 b1 + a2 r2 ; a*, b* as (re, im), r2 real
+template <class C>
+GS_HD void fp2dot3r_28(Fq28<C>& r0, Fq28<C>& r1, const Fq28<C>& a00, const Fq28<C>& a01, const Fq28<C>& b00,
+                       const Fq28<C>& b01, const Fq28<C>& a10, const Fq28<C>& a11, const Fq28<C>& b10, const Fq28<C>& b11,
+                       const Fq28<C>& a20, const Fq28<C>& a21, const Fq28<C>& r2) {
+#if defined(GS_FQ28_CHECK)
+  fq28_mul_counter().fetch_add(6, std::memory_order_relaxed);  // 12 L^2 multiply-adds = 6 products' worth
+  fq28_mad_counter().fetch_add(12 * C::L * C::L, std::memory_order_relaxed);
+  for (const Fq28<C>* x : {&a00, &a01, &b00, &b01, &a10, &a11, &b10, &b11, &a20, &a21, &r2}) {
+    int64_t t = x->v[C::L - 1] < 0 ? -(int64_t)x->v[C::L - 1] : x->v[C::L - 1];
+    if (t >= (1 << 26)) {
+      fprintf(stderr, "Fp2 dot product (real operand): operand value out of range (top limb %lld)\n", (long long)t);
+      abort();
+    }
+  }
+  const limb_t* a[6] = {a00.v, a01.v, a10.v, a11.v, a20.v, a21.v};
+  const limb_t* b[4] = {b00.v, b01.v, b10.v, b11.v};
+  fp2dot3r_28_generic<C, limb_t>(r0.v, r1.v, a, b, r2.v);
+  GS_CHK_LIMBS(r0)
+  GS_CHK_LIMBS(r1)
+#elif defined(__HIP_DEVICE_COMPILE__) && !defined(GS_NO_ASM) && !defined(GS_NO_ASM_CALL)
+  if constexpr (C::L == 14)
+    fp2dot3r_28_call_14<C>(r0.v, r1.v, a00.v, a01.v, b00.v, b01.v, a10.v, a11.v, b10.v, b11.v, a20.v, a21.v, r2.v);
+  else
+    fp2dot3r_28_call_10<C>(r0.v, r1.v, a00.v, a01.v, b00.v, b01.v, a10.v, a11.v, b10.v, b11.v, a20.v, a21.v, r2.v);
+#else
+  const int32_t* a[6] = {a00.v, a01.v, a10.v, a11.v, a20.v, a21.v};
+  const int32_t* b[4] = {b00.v, b01.v, b10.v, b11.v};
+  fp2dot3r_28_generic<C, int32_t>(r0.v, r1.v, a, b, r2.v);
 #endif
 }
 

@@ -808,34 +808,46 @@ struct k_miller {
 };
 
 // ---- pair-cooperative twin (multi_miller_pair): two lanes per (equation, task), one accumulator each ----------------
-// Exchange policies: how a lane hands its tangent / chord line (6 L dwords) to its partner lane ^ 1 (put / get, see
-// multi_miller_pair).
-//  * PairLds: a 16-byte-interleaved LDS slot per lane, [6 L / 4][64] x int4 (conflict-free ds_write_b128 / ds_read_b128,
-//    21 + 21 instructions for BLS12-381); the block is ONE wave, so program order is LDS order and the barriers below
+// Exchange policies: how a lane hands its tangent / chord line (real form: 5 L dwords) to its partner lane ^ 1 (put /
+// get, see multi_miller_pair).
+//  * PairLds: a 16-byte-interleaved LDS slot per lane, [ceil(5 L / 4)][64] x int4 (conflict-free ds_write_b128 /
+//    ds_read_b128, 18 + 18 instructions for BLS12-381, 18 KB; 21 + 21 and 21 KB with general lines); the block is ONE wave, so program order is LDS order and the barriers below
 //    are compiler fences; the partner's line is fetched only after the lane's own line product;
 //  * PairDpp: one v_mov_b32 with quad_perm [1,0,3,2] per dword at put(), no memory at all.
 // Measured at 2^16 (one box, alternating).  First shape of the round loop: DPP 157.1-158.9 ms, LDS 161.3-161.6 ms.
 // Final shape (the products of a round in one lambda, gs_pairing.cuh): LDS **147.5-147.7 ms**, DPP 154.6-156.0 ms on
 // BLS12-381 (a line parked in LDS frees 84 registers across the lane's own product); BN254 100.5 (DPP) against
 // 101.3 ms (LDS).  The planner takes LDS on BLS12-381 and DPP on BN254 (profiles/r3/ab_exchange.txt).
+// (a line is LINE_WORDS dwords: 5 L in the real form -- l0, lx in Fp2, ly in Fq --, 6 L under GS_LINES_GENERAL)
+template <class C> constexpr int line_words() { return (int)(sizeof(Line<C>) / sizeof(int32_t)); }
 template <class C> GS_HD int32_t& line_word(Line<C>& l, int i) {
   constexpr int L = C::L;
   const int c = i / L, j = i % L;
+#if defined(GS_LINES_GENERAL)
   return c == 0 ? l.l0.c0.v[j] : c == 1 ? l.l0.c1.v[j] : c == 2 ? l.lx.c0.v[j] : c == 3 ? l.lx.c1.v[j]
          : c == 4 ? l.ly.c0.v[j] : l.ly.c1.v[j];
+#else
+  return c == 0 ? l.l0.c0.v[j] : c == 1 ? l.l0.c1.v[j] : c == 2 ? l.lx.c0.v[j] : c == 3 ? l.lx.c1.v[j] : l.ly.v[j];
+#endif
 }
 template <class C> struct PairLds {
-  int4* slots;  // [6 L / 4][64]
+  int4* slots;  // [W][64]
   int lane;
-  static constexpr int W = 6 * C::L / 4;
-  static_assert(6 * C::L % 4 == 0, "a line is a whole number of 16-byte words");
+  // 16-byte words of a slot: 5 L = 70 / 50 dwords are 17.5 / 12.5 of them, the last word is half padding (written as 0,
+  // not read back).  Lane l's q-th word sits at int4 index 64 q + l: a ds_write_b128 / ds_read_b128 of the wave touches 64
+  // consecutive 16-byte words whatever W is, conflict-free as before; lane ^ 1 only swaps neighbours inside that run.
+  static constexpr int NW = line_words<C>();
+  static constexpr int W = (NW + 3) / 4;
   __device__ __forceinline__ void put(const Line<C>& mine) const {
     Line<C> m = mine;
     __syncthreads();  // (the partner has read the previous line: one wave per block, this only orders the compiler)
 #pragma unroll
-    for (int q = 0; q < W; q++)
-      slots[q * 64 + lane] = make_int4(line_word(m, 4 * q), line_word(m, 4 * q + 1), line_word(m, 4 * q + 2),
-                                       line_word(m, 4 * q + 3));
+    for (int q = 0; q < W; q++) {
+      int w[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) w[e] = 4 * q + e < NW ? line_word(m, 4 * q + e < NW ? 4 * q + e : 0) : 0;
+      slots[q * 64 + lane] = make_int4(w[0], w[1], w[2], w[3]);
+    }
     __syncthreads();
   }
   __device__ __forceinline__ Line<C> get() const {
@@ -843,10 +855,10 @@ template <class C> struct PairLds {
 #pragma unroll
     for (int q = 0; q < W; q++) {
       int4 v = slots[q * 64 + (lane ^ 1)];
-      line_word(r, 4 * q) = v.x;
-      line_word(r, 4 * q + 1) = v.y;
-      line_word(r, 4 * q + 2) = v.z;
-      line_word(r, 4 * q + 3) = v.w;
+      const int w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+        if (4 * q + e < NW) line_word(r, 4 * q + e) = w[e];
     }
     return r;
   }
@@ -856,7 +868,7 @@ template <class C> struct PairDpp {
   __device__ __forceinline__ void put(const Line<C>& mine) {
     Line<C> m = mine;
 #pragma unroll
-    for (int i = 0; i < 6 * C::L; i++)
+    for (int i = 0; i < line_words<C>(); i++)
       line_word(got, i) = __builtin_amdgcn_mov_dpp(line_word(m, i), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
   }
   __device__ __forceinline__ Line<C> get() const { return got; }
@@ -868,7 +880,7 @@ template <class C, bool DPP>
 struct k_miller_pair {
   static __device__ __forceinline__ void run(size_t g, size_t total, int ntask, const MillerTask* tasks, ArrTab parr,
                                                     ArrTab qarr, Fp12<C>* out, const Line<C>* ltab) {
-  __shared__ int4 xslots[DPP ? 1 : (6 * C::L / 4) * 64];
+  __shared__ int4 xslots[DPP ? 1 : PairLds<C>::W * 64];
   if (g >= total) return;  // total is even: a pair leaves together
   const int a = (int)(g & 1);
   const size_t gp = g >> 1, N = total / (2 * (size_t)ntask);

@@ -24,9 +24,55 @@ namespace gs {
 template <class C> struct Proj2 {  // homogeneous projective point on the twist
   Fp2<C> x, y, z;
 };
-template <class C> struct Line {
+template <class C> struct GLine {  // a tangent / chord line as the steps below leave it: three Fp2 coefficients
   Fp2<C> l0, lx, ly;
 };
+// REAL-FORM lines.  A line may be multiplied by any non-zero element of Fp2 (a proper subfield: it vanishes under the
+// final exponentiation, see above).  Multiplied by conj(ly) its y coefficient becomes the norm ly.c0^2 + ly.c1^2, an
+// element of Fq: the evaluated coefficient N(ly) yP is then REAL, one Fq product instead of two, and the sparse product
+// takes it as the real operand of its six dot products (f12_mul_by_014r / _034r: 72 L^2 multiply-adds instead of 84).
+// `Line` is the form in which a line is kept, exchanged between the lanes of a pair and tabulated: l0, lx in Fp2, ly in
+// Fq (5 L dwords instead of 6 L).  -DGS_LINES_GENERAL keeps the general form everywhere (the A/B partner).
+#if defined(GS_LINES_GENERAL)
+template <class C> using Line = GLine<C>;
+template <class C> GS_HD Line<C> line_real(const GLine<C>& l) { return l; }
+template <class C> GS_HD Line<C> line_unit(const GLine<C>& l) { return l; }
+#else
+template <class C> struct Line {
+  Fp2<C> l0, lx;
+  Fq<C> ly;
+};
+// l * conj(ly): two Fp2 products and two Fq squarings (~15 L^2), once per stepped line, for 12 + 2 L^2 saved at EVERY
+// accumulator the line goes into (the twin and lane-pair loops: two).  ly = 0 (T = +-Q or a point of order 2: not for
+// arguments of order r, kept so that no input changes its result): the line already is a real form of itself and comes
+// back unchanged with ly' = 0 -- selected word by word, the products see no special case.  (The exact test sits behind
+// is_zero's limb filter, which passes a non-zero value with probability 2^-30.)
+template <class C> GS_HD Line<C> line_real(const GLine<C>& l) {
+  const bool z = is_zero(l.ly);
+  const Fp2<C> cj = conj(l.ly);
+  Line<C> r;
+  r.l0 = select(z, l.l0, mul(l.l0, cj));
+  r.lx = select(z, l.lx, mul(l.lx, cj));
+  r.ly = add(sqr(l.ly.c0), sqr(l.ly.c1));  // A = 2: meets yP (A = 1) in one Fq product; = 0 mod p when ly is
+  return r;
+}
+// l / ly: the form of the line TABLES (one Fp2 inversion per line, once per CRS); the real coefficient is 1.  ly = 0:
+// stored unscaled with ly' = 0.
+template <class C> GS_HD Line<C> line_unit(const GLine<C>& l) {
+  Line<C> r;
+  if (is_zero(l.ly)) {
+    r.l0 = l.l0;
+    r.lx = l.lx;
+    r.ly = fq_zero<C>();
+    return r;
+  }
+  const Fp2<C> i = inv(l.ly);
+  r.l0 = mul(l.l0, i);
+  r.lx = mul(l.lx, i);
+  r.ly = fq_one<C>();
+  return r;
+}
+#endif
 
 template <class C> GS_HD Fp2<C> twist_b3() {
   Fp2<C> r;
@@ -42,7 +88,7 @@ template <class C> GS_HD Fp2<C> twist_b3() {
 // classical (X3, Y3, Z3) scaled by 4 -- the same projective point, no halvings:
 //   X3 = 2XY (B - F), Y3 = (B + F)^2 - 12 E^2, Z3 = 4 B H
 // with B = Y^2, E = 3 b' Z^2, F = 3E, H = 2YZ.
-template <class C> GS_ML void miller_dbl(Proj2<C>& t, Line<C>& l) {
+template <class C> GS_ML void miller_dbl(Proj2<C>& t, GLine<C>& l) {
   Fp2<C> xy = mul(t.x, t.y);
   Fp2<C> b = sqr(t.y);
   Fp2<C> c = sqr(t.z);
@@ -71,7 +117,7 @@ template <class C> GS_ML void miller_dbl(Proj2<C>& t, Line<C>& l) {
 }
 
 // T <- T + Q (Q affine on the twist), returns the chord line coefficients (all N).
-template <class C> GS_ML void miller_add(Proj2<C>& t, Line<C>& l, const Aff<Fp2<C>>& q) {
+template <class C> GS_ML void miller_add(Proj2<C>& t, GLine<C>& l, const Aff<Fp2<C>>& q) {
   Fp2<C> theta = norm(sub(t.y, mul(q.y, t.z)));
   Fp2<C> lambda = norm(sub(t.x, mul(q.x, t.z)));
   Fp2<C> c = sqr(theta);
@@ -94,8 +140,31 @@ template <class C> GS_ML void miller_add(Proj2<C>& t, Line<C>& l, const Aff<Fp2<
 template <class C> struct LineAcc {
   ELine<C> pend;
   bool has = false;
+#if !defined(GS_LINES_GENERAL)
+  // a real-form line: two Fq products for lx xP, one for ly yP, the sparse product with a real operand
   GS_HD void add(Fp12<C>& f, const Line<C>& l, const Aff<Fq<C>>& p) {
-    Fp2<C> cx = mul_fp(l.lx, p.x), cy = mul_fp(l.ly, p.y);
+    const Fp2<C> cx = mul_fp(l.lx, p.x);
+    const Fq<C> cy = mul(l.ly, p.y);
+#if defined(GS_LINES2_ALL)
+    GLine<C> g;  // (the paired form takes general coefficients)
+    g.l0 = l.l0, g.lx = cx, g.ly = Fp2<C>{cy, fq_zero<C>()};
+    add_evaluated(f, g);
+#else
+    if (C::TWIST_M)
+      f12_mul_by_014r(f, l.l0, cx, cy);
+    else
+      f12_mul_by_034r(f, cy, cx, l.l0);
+#endif
+  }
+#endif
+  GS_HD void add(Fp12<C>& f, const GLine<C>& l, const Aff<Fq<C>>& p) {
+    GLine<C> g;
+    g.l0 = l.l0, g.lx = mul_fp(l.lx, p.x), g.ly = mul_fp(l.ly, p.y);
+    add_evaluated(f, g);
+  }
+  // l.lx, l.ly already multiplied by the coordinates of P
+  GS_HD void add_evaluated(Fp12<C>& f, const GLine<C>& l) {
+    const Fp2<C>&cx = l.lx, &cy = l.ly;
 #if defined(GS_LINES2_ALL)
     constexpr bool pair_lines = true;
 #elif defined(GS_LINES2_NONE)
@@ -160,13 +229,16 @@ template <class C> GS_HD_NOINLINE void miller_line_table(Line<C>* out, const Aff
   t.y = q.y;
   t.z = one_of<Fp2<C>>();
   int n = 0;
+  GLine<C> l;
   for (int i = C::LOOP_LEN - 2; i >= 0; i--) {
-    miller_dbl(t, out[n++]);
+    miller_dbl(t, l);
+    out[n++] = line_unit(l);
     int d = C::LOOP[i];
     if (d != 0) {
       Aff<Fp2<C>> qq = q;
       if (d < 0) qq.y = neg(qq.y);
-      miller_add(t, out[n++], qq);
+      miller_add(t, l, qq);
+      out[n++] = line_unit(l);
     }
   }
   if (C::IS_BN) {
@@ -175,8 +247,10 @@ template <class C> GS_HD_NOINLINE void miller_line_table(Line<C>* out, const Aff
     q1.y = mul(conj(q.y), frob_coeff<C>(1, 3));
     q2.x = mul(q.x, frob_coeff<C>(2, 2));
     q2.y = neg(mul(q.y, frob_coeff<C>(2, 3)));
-    miller_add(t, out[n++], q1);
-    miller_add(t, out[n++], q2);
+    miller_add(t, l, q1);
+    out[n++] = line_unit(l);
+    miller_add(t, l, q2);
+    out[n++] = line_unit(l);
   }
 }
 
@@ -200,7 +274,9 @@ GS_HD_NOINLINE void multi_miller(Fp12<C>& fout, const Aff<Fq<C>>* ps, const Aff<
     fout = f;
     return;
   }
-  Line<C> l;
+  // Stepped lines keep the GENERAL product here: with one accumulator the scaling is a wash on paper (~15 L^2 spent,
+  // 14 saved per line).  The tabulated lines are real-form (Line<C>) and go through the real product.
+  GLine<C> l;
   LineAcc<C> acc;
   int li = 0;  // position in the line tables of the fixed arguments
   for (int i = C::LOOP_LEN - 2; i >= 0; i--) {
@@ -285,6 +361,7 @@ GS_HD_NOINLINE void multi_miller2(Fp12<C>& f0out, Fp12<C>& f1out, const Aff<Fq<C
     ts[k].z = one_of<Fp2<C>>();
   }
   if (!any) return;
+  GLine<C> g;  // the stepped line, and its real form: scaled ONCE, evaluated at both G1 components
   Line<C> l;
   LineAcc<C> acc0, acc1;
   int li = 0;
@@ -298,8 +375,10 @@ GS_HD_NOINLINE void multi_miller2(Fp12<C>& f0out, Fp12<C>& f1out, const Aff<Fq<C
       const Line<C>* lp = &l;
       if (fixed && fixed[k])
         lp = &fixed[k][li];
-      else
-        miller_dbl(ts[k], l);
+      else {
+        miller_dbl(ts[k], g);
+        l = line_real(g);
+      }
       if (live[k] & 1) acc0.add(f0, *lp, p0[k]);
       if (live[k] & 2) acc1.add(f1, *lp, p1[k]);
     }
@@ -314,7 +393,8 @@ GS_HD_NOINLINE void multi_miller2(Fp12<C>& f0out, Fp12<C>& f1out, const Aff<Fq<C
         } else {
           Aff<Fp2<C>> q = qs[k];
           if (d < 0) q.y = neg(q.y);
-          miller_add(ts[k], l, q);
+          miller_add(ts[k], g, q);
+          l = line_real(g);
         }
         if (live[k] & 1) acc0.add(f0, *lp, p0[k]);
         if (live[k] & 2) acc1.add(f1, *lp, p1[k]);
@@ -337,10 +417,12 @@ GS_HD_NOINLINE void multi_miller2(Fp12<C>& f0out, Fp12<C>& f1out, const Aff<Fq<C
       q1.y = mul(conj(qs[k].y), frob_coeff<C>(1, 3));
       q2.x = mul(qs[k].x, frob_coeff<C>(2, 2));
       q2.y = neg(mul(qs[k].y, frob_coeff<C>(2, 3)));
-      miller_add(ts[k], l, q1);
+      miller_add(ts[k], g, q1);
+      l = line_real(g);
       if (live[k] & 1) acc0.add(f0, l, p0[k]);
       if (live[k] & 2) acc1.add(f1, l, p1[k]);
-      miller_add(ts[k], l, q2);
+      miller_add(ts[k], g, q2);
+      l = line_real(g);
       if (live[k] & 1) acc0.add(f0, l, p0[k]);
       if (live[k] & 2) acc1.add(f1, l, p1[k]);
     }
@@ -357,7 +439,7 @@ GS_HD_NOINLINE void multi_miller2(Fp12<C>& f0out, Fp12<C>& f1out, const Aff<Fq<C
 // the same (equation, task): lane a owns the accumulator of component a for the whole loop (ONE accumulator per lane:
 // it fits the register file, the two of multi_miller2 do not and stream through memory at every line product), the
 // stepping twist points of the task are dealt out alternately (lane a steps triples a, a + 2, ...), and every tangent /
-// chord line crosses to the partner lane once through the exchange policy X (LDS slots or DPP on the device).  Total
+// chord line (in its real form, see Line) crosses to the partner lane once through the exchange policy X (LDS slots or DPP on the device).  Total
 // work is that of the twin loop: the same squarings per accumulator, every line computed once and evaluated at both
 // G1 components (data_structures.rs:494-502).
 //   ps[k]     the lane's OWN G1 component of every triple, k < np (stepping triples first: k < nstep)
@@ -384,7 +466,8 @@ GS_HD void multi_miller_pair(Fp12<C>& fout, int a, const Aff<Fq<C>>* ps, const A
     ts[r].y = q.y;
     ts[r].z = one_of<Fp2<C>>();
   }
-  Line<C> l, lp;
+  GLine<C> l;
+  Line<C> lp;
   LineAcc<C> acc;
   int li = 0;
   // The products of one round: the lane's own line at its own P, the partner's line at the lane's P for the partner's
@@ -393,7 +476,10 @@ GS_HD void multi_miller_pair(Fp12<C>& fout, int a, const Aff<Fq<C>>* ps, const A
   // lane 0 owes its own line, lane 1 the partner's -- taken as two branches the wave would run two products of which
   // each lane uses one (until round 3 it did: a lane of 1 stepping triple cost as much as one of 2, 9.2 ms instead of
   // ~6.5 ms for the 20-task plans of small batches).  So: one product slot whose operands are selected per lane.
-  auto products = [&](const Line<C>& mine, int ko, int kp) {
+  // The stepped line is brought to its real form ONCE, before it is used or handed over: both lanes then run the real
+  // product on it, and the exchange carries five Fq instead of six.
+  auto products = [&](const GLine<C>& stepped, int ko, int kp) {
+    const Line<C> mine = line_real(stepped);
     const bool own_ok = ko < nstep && ((live >> ko) & 1), par_ok = kp < nstep && ((live >> kp) & 1);
     xch.put(mine);
     if (own_ok && par_ok) {
@@ -406,7 +492,7 @@ GS_HD void multi_miller_pair(Fp12<C>& fout, int a, const Aff<Fq<C>>* ps, const A
         Line<C> use;  // (word-wise selects, not a branch per operand: a branch would bring the two products back)
         use.l0 = select(own_ok, mine.l0, lp.l0);
         use.lx = select(own_ok, mine.lx, lp.lx);
-        use.ly = select(own_ok, mine.ly, lp.ly);
+        use.ly = select(own_ok, mine.ly, lp.ly);  // (Fq in the real form: the select moves five Fq, not six)
         acc.add(f, use, ps[own_ok ? ko : kp]);
       }
     }
