@@ -2607,6 +2607,10 @@ template <class C> struct WireImpl {
         RC(launch(c, "k_wire_gt_check", k_wire_gt_check<C>, n, 64, n, (const uint8_t*)dout, (uint8_t*)dok2));
         RC(st.back(ok, dok2, n));
       }
+      // a rejected element decodes to zero as a whole: k_wire_fq clears only the coefficient that is out of range, and
+      // the torsion check runs after the values went back
+      for (size_t i = 0; i < n; i++)
+        if (!ok[i]) memset((uint8_t*)out + i * per * eb, 0, per * eb);
     }
     return GS_OK;
   }

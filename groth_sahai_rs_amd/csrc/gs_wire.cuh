@@ -357,6 +357,9 @@ GS_HD_NOINLINE bool wire_decode_point(Aff<F>& p, const uint8_t* in, bool compres
     coord_words<C>(got, y);
     if (y_is_largest<C, NC>(got) != largest) y = neg(y);
   } else {
+    // BN254 carries the sort flag on y as well.  ark-ec ignores it there; as for the identity, only the byte string the
+    // serialiser produces is accepted, so an uncompressed point has one encoding too.
+    if (C::IS_BN && y_is_largest<C, NC>(yw) != largest) return false;
     coord_from_words<C>(y, yw);
     if (!eq(sqr(y), rhs)) return false;
   }

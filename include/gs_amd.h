@@ -425,9 +425,11 @@ int gs_gt_pow_batch_dev(gs_ctx*, size_t count, const void* base_gt_dev, const vo
  * include/gs_amd.hpp, groth_sahai_rs_amd/wire.py.  Host pointers.  decode: ok[i] = 1 iff element i is a
  * well-formed encoding (canonical coordinates, consistent flags, on the curve) and, with validate != 0,
  * passes the r-torsion check of ark-serialize's Validate::Yes; rejected elements decode to the identity
- * (points) / zero.  The identity has exactly ONE accepted encoding (infinity flag, all-zero payload, no sort flag):
- * ark-bls12-381 ignores the payload once it sees the infinity flag, this decoder does not (stricter; arkworks'
- * own serialiser never produces the other byte strings).  sizes: out[0..5] = G1 compressed, G1 uncompressed, G2 compressed, G2 uncompressed, Fr, GT. */
+ * (points) / zero (Fr; GT: all twelve coefficients).  Every element has exactly ONE accepted encoding per form.  The
+ * identity is the infinity flag, an all-zero payload and no sort flag: ark-bls12-381 ignores the payload once it sees the
+ * infinity flag, this decoder does not.  A BN254 uncompressed point carries the sort flag of its y: ark-ec ignores that
+ * flag next to an explicit y, this decoder does not.  (Stricter in both; arkworks' own serialiser never produces the other
+ * byte strings.)  sizes: out[0..5] = G1 compressed, G1 uncompressed, G2 compressed, G2 uncompressed, Fr, GT. */
 int gs_wire_sizes(int curve_id, size_t out[6]);
 int gs_wire_encode_g1(gs_ctx*, size_t n, int compressed, const void* pts_g1, uint8_t* out);
 int gs_wire_encode_g2(gs_ctx*, size_t n, int compressed, const void* pts_g2, uint8_t* out);

@@ -170,6 +170,10 @@ def dec_point(b, group, compressed, validate=True):
             y = (-y) % O.P if nc == 1 else O.f2_neg(y)
     else:
         y = ys[0] if nc == 1 else tuple(ys)
+        if not zcash and _largest(y) != largest:
+            # stricter than ark-ec, which ignores the sort flag next to an explicit y: as for the identity, only the byte
+            # string the serialiser produces is accepted, so that no element has two encodings
+            raise ValueError("sort flag does not match y")
         if (y * y % O.P if nc == 1 else O.f2_sqr(y)) != rhs:
             raise ValueError("not on the curve")
     pt = (x, y)

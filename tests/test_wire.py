@@ -143,3 +143,63 @@ def test_device_decoder_rejects_what_the_oracle_rejects(twin, cname):  # noqa: F
                 buf = bytearray(b"".join(v.to_bytes(n, "little") for v in xs))
             seen.add((both(buf, group, True, validate=False), both(buf, group, True, validate=True)))
         assert (0, 0) in seen and ((1, 0) in seen or (cname == "bn254" and group == 1 and (1, 1) in seen))
+
+
+# ---- the adversarial tables of tests/wirevec.py ---------------------------------------------------------------------
+import wirevec  # noqa: E402
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_wirevec_table_is_what_it_claims(cname):
+    yielded = wirevec.selfcheck(cname)
+    for group in (1, 2):
+        assert set(wirevec.MUST_YIELD[(cname, group)]) <= set(yielded[group])
+
+
+@pytest.mark.parametrize("cname", CURVES)
+@pytest.mark.parametrize("group", [1, 2])
+@pytest.mark.parametrize("compressed", [True, False])
+def test_device_decoder_on_adversarial_encodings(twin, cname, group, compressed):  # noqa: F811
+    """Every case of the table through the host compile of wire_decode_point / wire_encode_point: the oracle's verdict
+    with and without validation, its value limb for limb, the identity on reject, and the bytes back in both forms."""
+    c = curve(cname)
+    enc, dec = getattr(twin, "twin_wire_enc_" + cname), getattr(twin, "twin_wire_dec_" + cname)
+    cases = wirevec.point_cases(cname, group, compressed)
+    setc(cname)
+    nl = (2 if group == 1 else 4) * c.nq
+    bad = []
+    for k in cases:
+        buf = np.frombuffer(k.data, dtype=np.uint8).copy()
+        for validate, want in ((1, k.ok_v), (0, k.ok_nv)):
+            out = np.full(nl, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+            got = dec(group, int(compressed), validate, ptr(buf), ptr(out))
+            why = k.why_v if validate else k.why_nv
+            if got != int(want):
+                bad.append((k.name, "validate=%d" % validate, "device %d" % got, "oracle: %s" % (why or "accepted")))
+            elif not want:
+                if out.any():
+                    bad.append((k.name, "validate=%d" % validate, "rejected but not the identity"))
+            else:
+                if not (out == wirevec.point_limbs(cname, k.value, group)).all():
+                    bad.append((k.name, "validate=%d" % validate, "decoded value"))
+                for form in (compressed, not compressed):
+                    back = np.zeros(sizes(c, group, form), dtype=np.uint8)
+                    enc(group, int(form), ptr(out), ptr(back))
+                    if back.tobytes() != (k.data if form == compressed else W.enc_point(k.value, group, form)):
+                        bad.append((k.name, "validate=%d" % validate, "re-encoded, compressed=%d" % form))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("cname", CURVES)
+def test_device_encoder_at_the_sort_boundary(twin, cname):  # noqa: F811
+    """y = (p-1)/2 and (p+1)/2 sit on the two sides of "y > -y"; no curve point has such a y on either G1, and the
+    encoder does not look at the curve."""
+    c = curve(cname)
+    enc = getattr(twin, "twin_wire_enc_" + cname)
+    setc(cname)
+    for group in (1, 2):
+        for name, pt in wirevec.enc_point_cases(cname, group):
+            for compressed in (True, False):
+                got = np.zeros(sizes(c, group, compressed), dtype=np.uint8)
+                enc(group, int(compressed), ptr(wirevec.point_limbs(cname, pt, group)), ptr(got))
+                assert got.tobytes() == W.enc_point(pt, group, compressed), (group, name, compressed)
