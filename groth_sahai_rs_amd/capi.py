@@ -36,6 +36,7 @@ SYMBOLS = [
     "gs_multi_verify_batch_dev", "gs_multi_verify_batch_rlc_dev", "gs_gt_finalize_dev",
     "gs_prove_mixed_dev", "gs_prove_mixed", "gs_verify_mixed_dev", "gs_verify_mixed",
     "gs_rerandomize_batch_dev", "gs_rerandomize_batch", "gs_rerandomize_statement_dev", "gs_rerandomize_statement",
+    "gs_set_extraction_key", "gs_extract_g1_dev", "gs_extract_g2_dev", "gs_extract_g1", "gs_extract_g2",
 ]
 GS_MIXED_MAX = 8
 GS_MULTI_SHARED_DEVICES = 1
@@ -341,6 +342,36 @@ class Engine:
         return self._rerand_host("gs_rerandomize_statement", True, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
                                  R, S, T)
 
+    def set_extraction_key(self, key):
+        """Install the binding key (a1, a2) of the installed CRS: two Montgomery Fr (gs_set_extraction_key); None
+        forgets it.  A wrong key or a hiding CRS raises GsError code 3 and installs nothing."""
+        if key is None:
+            self._chk(self.lib.gs_set_extraction_key(self.ctx, _p(None)))
+            return
+        key = np.ascontiguousarray(key).view(np.uint8).reshape(-1)
+        _need("gs_set_extraction_key", [("key", key, 2 * self.FR)])
+        self._chk(self.lib.gs_set_extraction_key(self.ctx, _p(key)))
+
+    def _check_extract(self, fn, group, coms, out=None):
+        """Byte lengths of an extraction: whole commitments in, one point per commitment out.  Returns the count."""
+        if group not in (1, 2):
+            raise GsError(3, "%s: group must be 1 or 2" % fn)
+        csz, gsz = (self.COM1, self.G1) if group == 1 else (self.COM2, self.G2)
+        n = _nbytes(coms) // csz
+        _need(fn, [("coms", coms, n * csz), ("out", out, n * gsz)])
+        return n
+
+    def extract(self, group, coms):
+        """out[i] = coms[i].1 - a coms[i].0 with the installed binding key (gs_extract_g1 / gs_extract_g2): the
+        committed G1 / G2 witness, or x * generator for a committed scalar x."""
+        coms = np.ascontiguousarray(coms).view(np.uint8).reshape(-1)
+        fn = "gs_extract_g1" if group == 1 else "gs_extract_g2"
+        n = self._check_extract(fn, group, coms)
+        gsz = self.G1 if group == 1 else self.G2
+        out = self._out(n * gsz)
+        self._chk(getattr(self.lib, fn)(self.ctx, ctypes.c_size_t(n), _p(coms), _p(out)))
+        return out.reshape(n, gsz)
+
     def verify_batch(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, ok=None):
         u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         if ok is None:
@@ -507,6 +538,11 @@ class Engine:
     def g_mul_batch_dev(self, group, n, points, broadcast, scalars, out):
         fn = self.lib.gs_g1_mul_batch_dev if group == 1 else self.lib.gs_g2_mul_batch_dev
         self._chk(fn(self.ctx, ctypes.c_size_t(n), _p(points), 1 if broadcast else 0, _p(scalars), _p(out)))
+
+    def extract_dev(self, group, coms, out):
+        fn = "gs_extract_g1_dev" if group == 1 else "gs_extract_g2_dev"
+        n = self._check_extract(fn, group, coms, out)
+        self._chk(getattr(self.lib, fn)(self.ctx, ctypes.c_size_t(n), _p(coms), _p(out)))
 
     def multi_pairing_batch_dev(self, n, k, P, Q, out):
         self._chk(self.lib.gs_multi_pairing_batch_dev(self.ctx, ctypes.c_size_t(n), k, _p(P), _p(Q), _p(out)))

@@ -137,6 +137,10 @@ struct gs_ctx {
   // argument packs hold raw device pointers, so nothing is freed until the replay has been enqueued and drained
   std::vector<void*> deferred_free;
   unsigned long long* stamp = nullptr;  // 3 x u64 on the device: the clock stamps of the launch being profiled
+  // binding key (gs_set_extraction_key), kept ONLY as its digit streams on the device: SharedDigits[4] = G1 with and
+  // without the endomorphism, G2 likewise.  They are the secret: zeroed when the key goes (clear_extraction_key).
+  DevBuf xkey;
+  bool have_xkey = false;
 };
 
 // Every live context of the process (gs_ctx_create .. gs_ctx_destroy): page-locked caller ranges are process-wide
@@ -2420,6 +2424,13 @@ template <class C> struct Impl {
 #endif
 
 #if defined(GS_ONLY_BLS)
+#define DISPATCH_FN(ctx, FN, ARGS) \
+  ((ctx)->curve == GS_CURVE_BLS12_381 ? FN<Bls12_381> ARGS : fail(ctx, GS_ERR_ARG, "built with GS_ONLY_BLS"))
+#else
+#define DISPATCH_FN(ctx, FN, ARGS) ((ctx)->curve == GS_CURVE_BLS12_381 ? FN<Bls12_381> ARGS : FN<Bn254> ARGS)
+#endif
+
+#if defined(GS_ONLY_BLS)
 #define WIRE_DISPATCH(expr_bls, expr_bn) (c->curve == 0 ? (expr_bls) : fail(c, GS_ERR_ARG, "built with GS_ONLY_BLS"))
 #else
 #define WIRE_DISPATCH(expr_bls, expr_bn) (c->curve == 0 ? (expr_bls) : (expr_bn))
@@ -2461,6 +2472,15 @@ struct HostStage {  // host<->device staging for the un-suffixed entry points
     return GS_OK;
   }
 };
+
+// Forget the binding key.  The digit streams on the device are the only copy the context keeps.
+static void clear_extraction_key(gs_ctx* c) {
+  c->have_xkey = false;
+  if (!c->xkey.p) return;
+  hipSetDevice(c->device);
+  hipStreamSynchronize(c->stream);  // extractions already enqueued still read the streams
+  hipMemset(c->xkey.p, 0, c->xkey.cap);
+}
 
 static int check_ctx(gs_ctx* c, bool need_crs) {
   if (!c) return GS_ERR_ARG;
@@ -2616,6 +2636,45 @@ template <class C> struct WireImpl {
   }
 };
 
+// ---- witness extraction with the binding key (entry points below) ----------------------------------------------------
+template <class C> static int set_extraction_key_impl(gs_ctx* c, const void* key) {
+  RC(ensure(c, c->xkey, 4 * sizeof(SharedDigits)));
+  SharedDigits* sd = (SharedDigits*)c->xkey.p;
+  void* stage;
+  RC(scratch(c, "xkey.in", 2 * SZ_FR + 4, &stage));
+  const Fr<C>* dk = (const Fr<C>*)stage;
+  uint8_t* dok = (uint8_t*)stage + 2 * SZ_FR;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(stage, key, 2 * SZ_FR, hipMemcpyHostToDevice));
+  int rc = launch(c, "k_extract_key.g1", k_extract_key<C, Fq<C>>, 2, 64, dk, (const uint8_t*)c->tabs->crs_g1.p, sd, dok);
+  if (rc == GS_OK)
+    rc = launch(c, "k_extract_key.g2", k_extract_key<C, Fp2<C>>, 2, 64, dk + 1, (const uint8_t*)c->tabs->crs_g2.p, sd + 2,
+                dok + 2);
+  uint8_t ok[4] = {0, 0, 0, 0};
+  hipError_t e = hipSuccess;
+  if (rc == GS_OK) e = hipMemcpyAsync(ok, dok, 4, hipMemcpyDeviceToHost, c->stream);
+  hipMemsetAsync(stage, 0, 2 * SZ_FR, c->stream);  // the staged key goes whatever happened
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  if (rc != GS_OK) return rc;
+  if (e != hipSuccess || e2 != hipSuccess) return fail(c, GS_ERR_DEVICE, "gs_set_extraction_key", e != hipSuccess ? e : e2);
+  static const char* const what[4] = {
+      "gs_set_extraction_key: u[0].1 != a1 * u[0].0 (wrong a1)",
+      "gs_set_extraction_key: u[1].1 != a1 * u[1].0 (a hiding CRS binds no witness, or wrong a1)",
+      "gs_set_extraction_key: v[0].1 != a2 * v[0].0 (wrong a2)",
+      "gs_set_extraction_key: v[1].1 != a2 * v[1].0 (a hiding CRS binds no witness, or wrong a2)"};
+  for (int i = 0; i < 4; i++)
+    if (!ok[i]) return fail(c, GS_ERR_ARG, what[i]);
+  c->have_xkey = true;
+  return GS_OK;
+}
+template <class C, class F> static int extract_impl(gs_ctx* c, const char* name, int slot, size_t n, const void* coms, void* out) {
+  const SharedDigits* sd = (const SharedDigits*)c->xkey.p + slot;
+  if (c->endo)
+    return launch_seg<k_extract<C, F, true>>(c, name, n, 64, n, (const uint8_t*)coms, sd, (uint8_t*)out);
+  return launch_seg<k_extract<C, F, false>>(c, (std::string(name) + ".plain").c_str(), n, 64, n, (const uint8_t*)coms,
+                                            sd + 1, (uint8_t*)out);
+}
+
 extern "C" {
 
 const char* gs_version(void) { return GS_VERSION; }
@@ -2682,6 +2741,8 @@ void gs_ctx_destroy(gs_ctx* c) {
   }
   hipSetDevice(c->device);
   drain_ctx(c);
+  clear_extraction_key(c);
+  if (c->xkey.p) hipFree(c->xkey.p);
   for (void* p : c->deferred_free) hipFree(p);
   if (c->stamp) hipFree(c->stamp);
   for (auto& kv : c->scratch)
@@ -2856,6 +2917,7 @@ int gs_host_free(gs_ctx* c, void* ptr) {
 int gs_set_crs(gs_ctx* c, const void* crs) {
   RC(check_ctx(c, false));
   if (!crs) return GS_ERR_ARG;
+  clear_extraction_key(c);  // a key belongs to the CRS it was checked against
   return DISPATCH(c, set_crs(c, crs));
 }
 
@@ -3405,6 +3467,56 @@ int gs_rerandomize_statement(gs_ctx* c, int ty, size_t E, int m, int n, const vo
   return rerand_host(c, RerandArgs{ty, E, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
                                    theta_out, true});
 }
+
+// ---- witness extraction with the binding key ---------------------------------------
+int gs_set_extraction_key(gs_ctx* c, const void* a1a2) {
+  RC(check_ctx(c, false));
+  clear_extraction_key(c);
+  if (!a1a2) return GS_OK;
+  RC(check_ctx(c, true));
+  if (c->rec) return fail(c, GS_ERR_ARG, "gs_set_extraction_key inside a mixed call");
+  int rc = DISPATCH_FN(c, set_extraction_key_impl, (c, a1a2));
+  if (rc != GS_OK) clear_extraction_key(c);  // a refused key leaves nothing behind
+  return rc;
+}
+
+static int extract_check(gs_ctx* c, size_t n, const void* coms, void* out, size_t pt) {
+  RC(check_ctx(c, true));
+  if (!c->have_xkey) return fail(c, GS_ERR_ARG, "gs_set_extraction_key has not been called");
+  if (n == 0) return GS_OK;
+  if (!coms || !out) return fail(c, GS_ERR_ARG, "null pointer");
+  const uint8_t *a = (const uint8_t*)coms, *b = (const uint8_t*)out;
+  if (a < b + n * pt && b < a + 2 * n * pt) return fail(c, GS_ERR_ARG, "gs_extract: out overlaps coms");
+  return GS_OK;
+}
+int gs_extract_g1_dev(gs_ctx* c, size_t n, const void* coms, void* out) {
+  RC(extract_check(c, n, coms, out, c ? 2 * sz_fq(c->curve) : 0));
+  if (n == 0) return GS_OK;
+  return WIRE_DISPATCH((extract_impl<Bls12_381, Fq<Bls12_381>>(c, "k_extract.g1", 0, n, coms, out)),
+                       (extract_impl<Bn254, Fq<Bn254>>(c, "k_extract.g1", 0, n, coms, out)));
+}
+int gs_extract_g2_dev(gs_ctx* c, size_t n, const void* coms, void* out) {
+  RC(extract_check(c, n, coms, out, c ? 4 * sz_fq(c->curve) : 0));
+  if (n == 0) return GS_OK;
+  return WIRE_DISPATCH((extract_impl<Bls12_381, Fp2<Bls12_381>>(c, "k_extract.g2", 2, n, coms, out)),
+                       (extract_impl<Bn254, Fp2<Bn254>>(c, "k_extract.g2", 2, n, coms, out)));
+}
+#define EXTRACT_HOST(NAME, DEVNAME, PT)                             \
+  int NAME(gs_ctx* c, size_t n, const void* coms, void* out) {      \
+    RC(check_ctx(c, true));                                         \
+    if (!c->have_xkey) return fail(c, GS_ERR_ARG, "gs_set_extraction_key has not been called"); \
+    if (n == 0) return GS_OK;                                       \
+    if (!coms || !out) return fail(c, GS_ERR_ARG, "null pointer"); \
+    size_t pt = (PT) * sz_fq(c->curve);                             \
+    HostStage st(c);                                                \
+    void *dc, *dout;                                                \
+    RC(st.in(coms, n * 2 * pt, &dc));                               \
+    RC(st.out(out, n * pt, &dout));                                 \
+    RC(DEVNAME(c, n, dc, dout));                                    \
+    return st.back(out, dout, n * pt);                              \
+  }
+EXTRACT_HOST(gs_extract_g1, gs_extract_g1_dev, 2)
+EXTRACT_HOST(gs_extract_g2, gs_extract_g2_dev, 4)
 
 // ---- helpers / hooks -----------------------------------------------------------
 int gs_g1_mul_batch_dev(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {

@@ -1095,4 +1095,96 @@ GS_HD void jac_msm_straus_at(Jac<F>& rout, const Aff<F>* ps, const Fr<C>* ks, in
   jac_straus_run<C, F, TMAX, 4>(rout, ks, nt, at, zback);
 }
 
+// ---------------------------------------------------------------------------
+// ONE scalar for a whole launch (k_extract: every lane multiplies its own point by the binding key).  The routines
+// above take a scalar per lane: each lane recodes it, and the digit decides per lane whether an addition runs and
+// which table entry it reads.  With a launch-wide scalar the digit streams are made once, before the launch
+// (shared_digits), and read through the scalar path here: every branch on a digit is wave-uniform (no lane idles
+// through another lane's addition, a zero digit costs nothing) and the table index is the same in all 64 lanes, so the
+// lane's private table is read at a uniform offset -- the interleaved rows that make a divergent index expensive
+// (jac_straus_run's header) are read whole.
+// ---------------------------------------------------------------------------
+constexpr int SHARED_MAXD = 104;  // BN254 G2: 4 streams x 25 digits is the longest
+struct SharedDigits {
+  int32_t top;             // highest window with a non-zero digit in any stream
+  uint32_t sgm;            // bit s: stream s enters negated
+  int8_t d[SHARED_MAXD];   // d[s * ND + i]: signed w = 4 digit i of stream s
+};
+// ENDO: the streams of endo_digits (r-torsion points only); else the signed-window digits of the full scalar
+template <class C, class F, bool ENDO> struct SharedShape {
+  static constexpr bool E = ENDO && C::HAS_ENDO;
+  static constexpr int NS = E ? EndoShape<C, F>::NS : 1;
+  static constexpr int ND = E ? EndoShape<C, F>::nd(4) : (FrM<C>::BITS + 3) / 4 + 1;
+  static_assert(NS * ND <= SHARED_MAXD, "digit streams of a launch-wide scalar");
+};
+// k: canonical scalar
+template <class C, class F, bool ENDO> GS_HD void shared_digits(SharedDigits& o, const Fr<C>& k) {
+  typedef SharedShape<C, F, ENDO> S;
+  for (int i = 0; i < SHARED_MAXD; i++) o.d[i] = 0;
+  o.sgm = 0;
+  if constexpr (S::E) {
+    uint8_t sg[S::NS];
+    endo_digits<C, 4>(o.d, sg, k, (const Jac<F>*)nullptr);
+    for (int s = 0; s < S::NS; s++) o.sgm |= (uint32_t)(sg[s] != 0) << s;
+  } else {
+    recode_w4<FrM<C>>(o.d, S::ND, k);
+  }
+  int top = 0;
+  for (int s = 0; s < S::NS; s++)
+    for (int i = S::ND - 1; i > top; i--)
+      if (o.d[s * S::ND + i] != 0) top = i;
+  o.top = top;
+}
+// a value every lane of the wave holds alike, as the compiler can see it: branches on it are scalar branches
+GS_HD int wave_uniform(int v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_readfirstlane(v);
+#else
+  return v;
+#endif
+}
+// r = k P, the digits of k in `sd` (the same for every lane of the launch).  Full edge-case handling: P may be the
+// identity, and with ENDO = false any curve point.
+template <class C, class F, bool ENDO>
+GS_HD_NOINLINE void jac_smul_shared(Jac<F>& rout, const Aff<F>& p, const SharedDigits* sd) {
+  typedef SharedShape<C, F, ENDO> S;
+  // point operations as in the per-lane routines of the same shape: the register-only subroutines where those use them
+  // (jac_smul_endo on G2, jac_straus_run on BN254), the C++ formulas on the plain path and on BLS12-381 G1
+  constexpr bool IP = S::E && (C::IS_BN || sizeof(F) != sizeof(Fq<C>));
+  Jac<F> r;  // local running sum (see jac_straus_run)
+  Jac<F> tab[8];
+  Aff<F> at[8];
+  F zback;
+  smul_build_table(tab, p);
+  table_global_z<C>(at, tab, 8, zback);
+  const int top = wave_uniform(sd->top);
+  const uint32_t sgm = (uint32_t)wave_uniform((int)sd->sgm);
+  jac_set_inf(r);
+  for (int i = top; i >= 0; i--) {
+    if (i != top) {
+#pragma unroll 1
+      for (int d4 = 0; d4 < 4; d4++) {
+        if constexpr (IP)
+          jac_dbl_ip(r);
+        else
+          jac_dbl(r, r);
+      }
+    }
+#pragma unroll 1
+    for (int s = 0; s < S::NS; s++) {
+      const int a = wave_uniform((int)sd->d[s * S::ND + i]);
+      if (a == 0) continue;  // wave-uniform: no lane waits for another lane's addition
+      Aff<F> t = at[(a < 0 ? -a : a) - 1];
+      if constexpr (S::E) endo_apply<C>(t, s);
+      if ((a < 0) != (((sgm >> s) & 1u) != 0)) t.y = neg(t.y);
+      if constexpr (IP)
+        jac_madd_ip(r, t);
+      else
+        jac_madd(r, r, t);
+    }
+  }
+  r.z = mul(r.z, zback);
+  rout = r;
+}
+
 }  // namespace gs

@@ -209,6 +209,60 @@ template <class C, class F> __global__ void k_crs_derive(uint8_t* pts) {
   aff_store<C>(pts + 5 * AFFB(C, F), r);
 }
 
+// ---- witness extraction with the binding key (gs_extract_*) -----------------------------------------------------------
+// The CRS of gs_crs_generate has u0 = (p, a p), u1 = t u0, so a commitment c = (O, X) + r0 u0 + r1 u1 opens to
+// X = c.1 - a c.0 for whoever holds a.  out[i] = coms[i].1 - a coms[i].0, one lane per commitment, `a` the same in every
+// lane: its digit streams are made once at key-set time (k_extract_key) and read here through the scalar path
+// (jac_smul_shared).  The subtraction is one more addition on the running point: a c.0 + (-c.1), negated -- the mixed
+// addition's own edge cases cover a c.0 = O, c.1 = O, a c.0 = c.1 (identity out) and a c.0 = -c.1 (doubling).
+template <class C, class F, bool ENDO = true>
+struct k_extract {
+  static __device__ __forceinline__ void run(size_t g, size_t total, const uint8_t* coms, const SharedDigits* sd,
+                                            uint8_t* out) {
+  if (g >= total) return;
+  Aff<F> c0, c1;
+  aff_load<C>(c0, coms + (2 * g) * AFFB(C, F));
+  aff_load<C>(c1, coms + (2 * g + 1) * AFFB(C, F));
+  Jac<F> J;
+  jac_smul_shared<C, F, ENDO>(J, c0, sd);
+  c1.y = neg(c1.y);  // (the identity (0, 0) stays exactly (0, 0))
+  jac_madd(J, J, c1);
+  J.y = neg(J.y);
+  Aff<F> R;
+  jac_to_aff(R, J);
+  aff_store<C>(out + g * AFFB(C, F), R);
+}
+};
+
+// Key-set time, lanes 0 and 1: does pts[2 i + 1] == key * pts[2 i] hold for the CRS pair i (u0, u1 or v0, v1)?  Plain
+// double-and-add, so the answer is defined whatever the CRS holds.  Lane 0 also writes the key's digit streams for the
+// endomorphism kernels (sd[0]) and the plain ones (sd[1]).  key: one Montgomery Fr.
+template <class C, class F>
+__global__ void __launch_bounds__(64, GS_WPE) k_extract_key(const Fr<C>* key, const uint8_t* pts, SharedDigits* sd,
+                                                            uint8_t* ok) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 2) return;
+  const Fr<C> k = from_mont(key[0]);
+  Aff<F> P, R;
+  aff_load<C>(P, pts + (2 * i) * AFFB(C, F));
+  Jac<F> J;
+  jac_smul(J, P, k);
+  jac_to_aff(R, J);
+  BFq<C> got[AFFB(C, F) / sizeof(BFq<C>)];
+  aff_store<C>(reinterpret_cast<uint8_t*>(got), R);
+  const uint8_t *a = reinterpret_cast<const uint8_t*>(got), *b = pts + (2 * i + 1) * AFFB(C, F);
+  bool same = true;
+  for (size_t j = 0; j < AFFB(C, F); j++) same = same && a[j] == b[j];
+  ok[i] = same ? 1 : 0;
+  if (i == 0) {
+    SharedDigits d;
+    shared_digits<C, F, true>(d, k);
+    sd[0] = d;
+    shared_digits<C, F, false>(d, k);
+    sd[1] = d;
+  }
+}
+
 // window tables: tab[(b*32 + w)*256 + d] = d * 2^(8w) * base[b]   (d = 0 -> identity)
 template <class C, class F>
 __global__ void __launch_bounds__(64, GS_WPE) k_build_tables(int nb, const uint8_t* bases, Aff<F>* tab) {

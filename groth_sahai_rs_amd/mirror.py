@@ -9,6 +9,7 @@ top of the C ABI (same names, argument meaning and error behaviour):
         .prove(xvars, yvars, xcoms, ycoms, crs, rng) -> EquProof
         .verify(com_proof, crs) -> bool                                    src/verifier.rs:18-21
     rerandomize(equ, com_proof, crs, rng) -> CProof                      (new) fresh commitments and proof, no witness
+    generate_crs_with_key -> (CRS, key), extract(commit, crs, key)        (new) open commitments with the binding key
     EquProof {pi, theta, equ_type, rand}, CProof {xcoms, ycoms, equ_proofs} prove.rs:55-69
 
 Values are numpy uint64 limb arrays in the boundary layout of include/gs_amd.h
@@ -39,12 +40,8 @@ class CRS:
         self.engine.set_crs(flat)
 
 
-def generate_crs(p1, p2, rng, curve=0, device=0, hiding=False):
-    """AbstractCrs::generate_crs (generator.rs:81-118) with the group generators supplied by the caller
-    (the reference draws them with G1::rand / G2::rand, which has no counterpart outside arkworks);
-    the four scalars a1, a2, t1, t2 are drawn from `rng` in the reference's order (generator.rs:90-93)."""
+def _crs_from_scalars(p1, p2, sc, curve, device, hiding):
     eng = Engine(curve, device)
-    sc = np.concatenate([rng.fr() for _ in range(4)])
     raw = eng.crs_generate(p1, p2, sc, hiding=hiding).view(np.uint64)  # hiding: generator.rs:65-77
     eng.close()
     g1, g2 = eng.G1 // 8, eng.G2 // 8
@@ -54,6 +51,37 @@ def generate_crs(p1, p2, rng, curve=0, device=0, hiding=False):
         parts.append(raw[o:o + sz].copy())
         o += sz
     return CRS([parts[0], parts[1]], [parts[2], parts[3]], parts[4], parts[5], parts[6], curve, device)
+
+
+def generate_crs(p1, p2, rng, curve=0, device=0, hiding=False):
+    """AbstractCrs::generate_crs (generator.rs:81-118) with the group generators supplied by the caller
+    (the reference draws them with G1::rand / G2::rand, which has no counterpart outside arkworks);
+    the four scalars a1, a2, t1, t2 are drawn from `rng` in the reference's order (generator.rs:90-93)."""
+    sc = np.concatenate([rng.fr() for _ in range(4)])
+    return _crs_from_scalars(p1, p2, sc, curve, device, hiding)
+
+
+def generate_crs_with_key(p1, p2, rng, curve=0, device=0, hiding=False):
+    """generate_crs that also hands out the binding key: (CRS, key), key = a1 || a2 (8 u64 limbs, Montgomery form).
+    The draws are those of generate_crs, so the same rng state gives the same CRS.  The key opens every commitment
+    made under this CRS (extract below): keep it secret, or drop it."""
+    sc = np.concatenate([rng.fr() for _ in range(4)])
+    return _crs_from_scalars(p1, p2, sc, curve, device, hiding), sc[:8].copy()
+
+
+def extract(commit, crs, key):
+    """What the commitments of a Commit1 / Commit2 bind, opened with the binding key of `crs`: c.1 - a c.0 for each
+    (gs_extract_g1 / gs_extract_g2).  A committed group element comes back itself; a committed scalar x comes back as
+    x * generator (its image: x itself is a discrete logarithm away).  Raises GsError (code 3) when `key` is not the
+    binding key of `crs`, in particular on a hiding CRS.  The key stays installed in crs.engine until
+    crs.engine.set_extraction_key(None)."""
+    group = 2 if isinstance(commit, Commit2) else 1
+    crs.engine.set_extraction_key(key)
+    n = len(commit.coms)
+    if n == 0:
+        return []
+    out = crs.engine.extract(group, _cat(commit.coms, 0))
+    return [out[i].view(np.uint64).copy() for i in range(n)]
 
 
 class Commit1:

@@ -247,6 +247,37 @@ int gs_rerandomize_statement(gs_ctx*, int equ_type, size_t E, int m, int n, cons
                              const void* theta, const void* R, const void* S, const void* T, void* xcoms_out,
                              void* ycoms_out, void* pi_out, void* theta_out);
 
+/* ---- extract (the binding key opens commitments) ---------------------------- */
+/* The CRS of gs_crs_generate is u0 = (p1, a1 p1), u1 = t1 u0 (and v with a2, t2, p2).  Whoever drew a1, a2 can open
+ * ANY commitment to the witness it binds:
+ *   G1 variable  c = (O, X) + r0 u0 + r1 u1  ->  c.1 - a1 c.0 = X
+ *   Fr variable  c = x W1 + r u0             ->  c.1 - a1 c.0 = x p1   (the witness's IMAGE: recovering x from it is a
+ *                                                 discrete logarithm, which nothing here attempts)
+ * and likewise in G2 with a2.  On the hiding key (gs_crs_generate_hiding) u1.1 = t1 a1 p1 - p1 and nothing can be
+ * extracted; that key is refused.
+ *
+ * gs_set_extraction_key: a1a2_fr2 is a HOST pointer to a1, a2 (two Fr, Montgomery limbs); NULL forgets the key.  Needs
+ * an installed CRS (GS_ERR_NOCRS) and checks u[0].1 == a1 u[0].0, u[1].1 == a1 u[1].0, v[0].1 == a2 v[0].0 and
+ * v[1].1 == a2 v[1].0 on the device: a wrong key or a hiding CRS returns GS_ERR_ARG, gs_last_error names the check that
+ * failed, and no key is installed (an earlier one is gone too).  The call synchronises the stream.  gs_set_crs forgets
+ * the key.  The key is a SECRET: the context keeps it only as digit streams in device memory, which are zeroed (as is
+ * the staged copy of the key itself) when the key is cleared or replaced, on gs_set_crs and on gs_ctx_destroy.  The
+ * caller's own buffer is the caller's to wipe.
+ *
+ * gs_extract_g1 / gs_extract_g2: out[i] = coms[i].1 - a coms[i].0 for count Com1 (a = a1, out in G1) or Com2 (a = a2,
+ * out in G2) elements, normalised affine, the identity all-zero bytes.  It is a map on ALL of Com, not only on honest
+ * commitments.  count = 0 is a no-op; GS_ERR_ARG while no key is installed; out must not overlap coms (GS_ERR_ARG on
+ * the _dev form; the host form stages).  The _dev forms enqueue on the context's stream without synchronising.
+ * INPUTS: opened commitments usually come from ANOTHER PARTY.  As on the other compute entry points (top of this
+ * file) nothing is checked, and with "endo" = 1 (the default) components outside the prime-order subgroups give
+ * UNDEFINED results: decode them with gs_wire_decode_* (validate = 1), run them through gs_validate_points[_dev], or
+ * set gs_set_option("endo", 0), under which the result is c.1 - a c.0 for ANY pair of curve points. */
+int gs_set_extraction_key(gs_ctx*, const void* a1a2_fr2);
+int gs_extract_g1_dev(gs_ctx*, size_t count, const void* coms_com1, void* out_g1);
+int gs_extract_g2_dev(gs_ctx*, size_t count, const void* coms_com2, void* out_g2);
+int gs_extract_g1(gs_ctx*, size_t count, const void* coms_com1, void* out_g1);
+int gs_extract_g2(gs_ctx*, size_t count, const void* coms_com2, void* out_g2);
+
 /* ---- verify (src/verifier.rs) ------------------------------------------- */
 /* ok[i] = 1 iff equation i verifies; exact reference semantics (four GT cell
  * equalities per equation). */

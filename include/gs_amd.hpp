@@ -13,6 +13,7 @@
 //     .prove(xvars, yvars, xcoms, ycoms, crs, rng)
 //     .verify(com_proof, crs) -> bool             src/verifier.rs:18-21   (Verifiable)
 //   EquProof {pi, theta, equ_type, rand}, CProof  src/prover/prove.rs:55-69
+//   CRS::generate_crs_with_key, CRS::set_extraction_key, CRS::extract   (new) open commitments with the binding key
 //
 // Values are byte strings in the boundary layout of gs_amd.h (arkworks' Montgomery
 // limbs).  `Rng` is any type with `Fr fr()`; draws happen in the reference's order
@@ -24,6 +25,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "gs_amd.h"
@@ -99,6 +101,11 @@ template <class T> inline std::vector<T> split(const Bytes& b, size_t n) {
   return o;
 }
 
+// (new) the binding key of a CRS: a1 opens Com1, a2 opens Com2 (CRS::generate_crs_with_key, CRS::extract)
+struct ExtractionKey {
+  Fr a1, a2;
+};
+
 struct CRS {  // generator.rs:35-42
   std::vector<Com1> u;
   std::vector<Com2> v;
@@ -125,12 +132,50 @@ struct CRS {  // generator.rs:35-42
   template <class Rng>
   static CRS generate_crs(const G1Affine& p1, const G2Affine& p2, Rng& rng, int curve = GS_CURVE_BLS12_381,
                           int device = 0) {
-    Ctx tmp(curve, device);
+    return from_scalars(p1, p2, draw_scalars(rng), curve, device);
+  }
+  // (new) generate_crs that also hands out the binding key a1, a2: the same draws, so the same rng state gives the same
+  // CRS.  The key opens every commitment made under this CRS (extract): keep it secret, or drop it.
+  template <class Rng>
+  static std::pair<CRS, ExtractionKey> generate_crs_with_key(const G1Affine& p1, const G2Affine& p2, Rng& rng,
+                                                             int curve = GS_CURVE_BLS12_381, int device = 0) {
+    Bytes sc = draw_scalars(rng);
+    ExtractionKey key{Fr{Bytes(sc.begin(), sc.begin() + 32)}, Fr{Bytes(sc.begin() + 32, sc.begin() + 64)}};
+    return {from_scalars(p1, p2, sc, curve, device), key};
+  }
+  // (new) Install the binding key in this CRS's context (gs_set_extraction_key).  Throws std::runtime_error when it is
+  // not the key of this CRS -- in particular on a hiding CRS, which binds nothing -- and installs nothing then.
+  void set_extraction_key(const ExtractionKey& key) const {
+    if (key.a1.v.size() != 32 || key.a2.v.size() != 32) throw Panic("assertion failed: Fr is 32 bytes");
+    Bytes k = key.a1.v;
+    k.insert(k.end(), key.a2.v.begin(), key.a2.v.end());
+    int rc = gs_set_extraction_key(ctx->c, k.data());
+    for (uint8_t& b : k) *(volatile uint8_t*)&b = 0;
+    ctx->chk(rc);
+  }
+  void clear_extraction_key() const { ctx->chk(gs_set_extraction_key(ctx->c, nullptr)); }
+  // (new) What the commitments bind, opened with the installed key: c.1 - a c.0 (gs_extract_g1 / gs_extract_g2).  A
+  // committed group element comes back itself, a committed scalar x as x * generator (its image; x itself is a
+  // discrete logarithm away).  Commitments from another party: validate them first, or run with "endo" 0 (gs_amd.h).
+  std::vector<G1Affine> extract(const std::vector<Com1>& coms) const {
+    return extract_impl<G1Affine>(coms, 2 * ctx->sz[2], ctx->sz[2], gs_extract_g1);
+  }
+  std::vector<G2Affine> extract(const std::vector<Com2>& coms) const {
+    return extract_impl<G2Affine>(coms, 2 * ctx->sz[3], ctx->sz[3], gs_extract_g2);
+  }
+
+ private:
+  template <class Rng> static Bytes draw_scalars(Rng& rng) {
     Bytes sc;
     for (int i = 0; i < 4; i++) {
       Fr s = rng.fr();
       sc.insert(sc.end(), s.v.begin(), s.v.end());
     }
+    return sc;
+  }
+  static CRS from_scalars(const G1Affine& p1, const G2Affine& p2, const Bytes& sc, int curve, int device) {
+    Ctx tmp(curve, device);
+    assert_eq(sc.size(), 4 * 32, "four scalars");
     Bytes raw(tmp.sz[5]);
     tmp.chk(gs_crs_generate(tmp.c, p1.v.data(), p2.v.data(), sc.data(), raw.data()));
     size_t g1 = tmp.sz[2], g2 = tmp.sz[3], o = 0;
@@ -145,6 +190,17 @@ struct CRS {  // generator.rs:35-42
     G2Affine b{take(g2)};
     GT t{take(tmp.sz[4])};
     return CRS(u, v, a, b, t, curve, device);
+  }
+  template <class P, class Com, class F>
+  std::vector<P> extract_impl(const std::vector<Com>& coms, size_t com_sz, size_t pt_sz, F fn) const {
+    for (const Com& c : coms) assert_eq(c.v.size(), com_sz, "commitment size");
+    if (coms.empty()) {  // (the key is still asked for: the C call checks it before the count)
+      ctx->chk(fn(ctx->c, 0, nullptr, nullptr));
+      return {};
+    }
+    Bytes in = cat(coms), out(coms.size() * pt_sz);
+    ctx->chk(fn(ctx->c, coms.size(), in.data(), out.data()));
+    return split<P>(out, coms.size());
   }
 };
 
