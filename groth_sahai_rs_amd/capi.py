@@ -104,6 +104,11 @@ def _p(a):
     return ctypes.c_void_p(a.data_ptr())
 
 
+def _u8(a):
+    """Flat uint8 view of anything numpy can hold contiguously."""
+    return np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+
+
 def _nbytes(a):
     if isinstance(a, np.ndarray):
         return a.nbytes
@@ -230,10 +235,9 @@ class Engine:
     def crs_generate(self, p1, p2, scalars, hiding=False):
         """CRS bytes of the reference's shape from generators p1, p2 and scalars (a1, a2, t1, t2); hiding=True gives
         the simulation key of generator.rs:65-77."""
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         out = self._out(self.CRS)
         fn = self.lib.gs_crs_generate_hiding if hiding else self.lib.gs_crs_generate
-        p1, p2, scalars = u8(p1), u8(p2), u8(scalars)  # named: the buffers must outlive the call
+        p1, p2, scalars = _u8(p1), _u8(p2), _u8(scalars)  # named: the buffers must outlive the call
         self._chk(fn(self.ctx, _p(p1), _p(p2), _p(scalars), _p(out)))
         return out
 
@@ -244,26 +248,32 @@ class Engine:
                     sy=self.G2 if yg else self.FR,
                     st={GS_PPE: self.GT, GS_MSMEG1: self.G1, GS_MSMEG2: self.G2, GS_QUAD: self.FR}[ty])
 
-    def _check_prove(self, fn, ty, N, m, n, X, Y, A, B, Gamma, R, S, T, xcoms=None, ycoms=None, pi=None, theta=None):
+    def _sizes(self, ty, N, m, n, shared=False):
+        """Bytes of every array of a batch: the table of csrc/gs_layout.h (tests/test_layout.py holds the two against
+        each other).  shared: a Statement -- ONE copy of X, Y, R, S and of the commitments for all N equations."""
+        sh = self.shape(ty)
+        kx, ky, sx, sy, fr, com1, com2 = sh["kx"], sh["ky"], sh["sx"], sh["sy"], self.FR, self.COM1, self.COM2
+        V = 1 if shared else N
+        return dict(X=V * m * sx, Y=V * n * sy, A=N * n * sx, B=N * m * sy, Gamma=N * m * n * fr, R=V * m * kx * fr,
+                    S=V * n * ky * fr, T=N * ky * kx * fr, target=N * sh["st"], xcoms=V * m * com1, ycoms=V * n * com2,
+                    pi=N * kx * com2, theta=N * ky * com1, ok=N)
+
+    def _check(self, fn, ty, N, m, n, shared, **arrays):
+        """Type, shape and the byte length of every array that is not None (`name_out` is sized like `name`).
+        Returns the size table."""
         if not (0 <= ty <= 3) or m < 1 or n < 1:
             raise GsError(1, "%s: bad equation type or empty variable list" % fn)
-        sh = self.shape(ty)
-        kx, ky, sx, sy = sh["kx"], sh["ky"], sh["sx"], sh["sy"]
-        _need(fn, [("X", X, N * m * sx), ("Y", Y, N * n * sy), ("A", A, N * n * sx), ("B", B, N * m * sy),
-                   ("Gamma", Gamma, N * m * n * self.FR), ("R", R, N * m * kx * self.FR),
-                   ("S", S, N * n * ky * self.FR), ("T", T, N * ky * kx * self.FR),
-                   ("xcoms", xcoms, N * m * self.COM1), ("ycoms", ycoms, N * n * self.COM2),
-                   ("pi", pi, N * kx * self.COM2), ("theta", theta, N * ky * self.COM1)])
+        want = self._sizes(ty, N, m, n, shared)
+        _need(fn, [(k, a, want[k[:-4] if k.endswith("_out") else k]) for k, a in arrays.items()])
+        return want
+
+    def _check_prove(self, fn, ty, N, m, n, X, Y, A, B, Gamma, R, S, T, xcoms=None, ycoms=None, pi=None, theta=None):
+        return self._check(fn, ty, N, m, n, False, X=X, Y=Y, A=A, B=B, Gamma=Gamma, R=R, S=S, T=T, xcoms=xcoms,
+                           ycoms=ycoms, pi=pi, theta=theta)
 
     def _check_verify(self, fn, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta):
-        if not (0 <= ty <= 3) or m < 1 or n < 1:
-            raise GsError(1, "%s: bad equation type or empty variable list" % fn)
-        sh = self.shape(ty)
-        kx, ky, sx, sy, st = sh["kx"], sh["ky"], sh["sx"], sh["sy"], sh["st"]
-        _need(fn, [("A", A, N * n * sx), ("B", B, N * m * sy), ("Gamma", Gamma, N * m * n * self.FR),
-                   ("target", target, N * st), ("xcoms", xcoms, N * m * self.COM1),
-                   ("ycoms", ycoms, N * n * self.COM2), ("pi", pi, N * kx * self.COM2),
-                   ("theta", theta, N * ky * self.COM1)])
+        return self._check(fn, ty, N, m, n, False, A=A, B=B, Gamma=Gamma, target=target, xcoms=xcoms, ycoms=ycoms,
+                           pi=pi, theta=theta)
 
     # -- host entry points (numpy uint8/uint64 arrays) --------------------------
     def _out(self, nbytes):
@@ -283,49 +293,31 @@ class Engine:
 
     def prove_batch(self, ty, N, m, n, X, Y, A, B, Gamma, R, S, T, want_coms=True, out=None):
         """`out`: dict of preallocated uint8 arrays xcoms, ycoms, pi, theta to write into (e.g. page-locked ones)."""
-        sh = self.shape(ty)
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        X, Y, A, B, Gamma, R, S, T = map(u8, (X, Y, A, B, Gamma, R, S, T))
-        self._check_prove("gs_prove_batch", ty, N, m, n, X, Y, A, B, Gamma, R, S, T)
+        X, Y, A, B, Gamma, R, S, T = map(_u8, (X, Y, A, B, Gamma, R, S, T))
+        want = self._check_prove("gs_prove_batch", ty, N, m, n, X, Y, A, B, Gamma, R, S, T)
         if out is not None:
             xc, yc, pi, th = (out.get(k) for k in ("xcoms", "ycoms", "pi", "theta"))
-            _need("gs_prove_batch", [("xcoms", xc, N * m * self.COM1), ("ycoms", yc, N * n * self.COM2),
-                                     ("pi", pi, N * sh["kx"] * self.COM2), ("theta", th, N * sh["ky"] * self.COM1)])
+            self._check_prove("gs_prove_batch", ty, N, m, n, *(None,) * 8, xc, yc, pi, th)
             if pi is None or th is None:
                 raise GsError(3, "gs_prove_batch: out needs pi and theta")
         else:
-            xc = self._out(N * m * self.COM1) if want_coms else None
-            yc = self._out(N * n * self.COM2) if want_coms else None
-            pi = self._out(N * sh["kx"] * self.COM2)
-            th = self._out(N * sh["ky"] * self.COM1)
-        self._chk(self.lib.gs_prove_batch(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(u8(X)), _p(u8(Y)), _p(u8(A)),
-                                          _p(u8(B)), _p(u8(Gamma)), _p(u8(R)), _p(u8(S)), _p(u8(T)), _p(xc), _p(yc),
-                                          _p(pi), _p(th)))
+            xc = self._out(want["xcoms"]) if want_coms else None
+            yc = self._out(want["ycoms"]) if want_coms else None
+            pi, th = self._out(want["pi"]), self._out(want["theta"])
+        self._chk(self.lib.gs_prove_batch(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(X), _p(Y), _p(A), _p(B), _p(Gamma),
+                                          _p(R), _p(S), _p(T), _p(xc), _p(yc), _p(pi), _p(th)))
         return dict(xcoms=xc, ycoms=yc, pi=pi, theta=th)
 
     def _check_rerand(self, fn, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T, outs=(None,) * 4,
                       shared=False):
-        if not (0 <= ty <= 3) or m < 1 or n < 1:
-            raise GsError(1, "%s: bad equation type or empty variable list" % fn)
-        sh = self.shape(ty)
-        kx, ky, sx, sy = sh["kx"], sh["ky"], sh["sx"], sh["sy"]
-        V = 1 if shared else N  # a Statement: one copy of the commitments and of R', S'
         xo, yo, po, to = outs
-        _need(fn, [("A", A, N * n * sx), ("B", B, N * m * sy), ("Gamma", Gamma, N * m * n * self.FR),
-                   ("xcoms", xcoms, V * m * self.COM1), ("ycoms", ycoms, V * n * self.COM2),
-                   ("pi", pi, N * kx * self.COM2), ("theta", theta, N * ky * self.COM1),
-                   ("R", R, V * m * kx * self.FR), ("S", S, V * n * ky * self.FR), ("T", T, N * ky * kx * self.FR),
-                   ("xcoms_out", xo, V * m * self.COM1), ("ycoms_out", yo, V * n * self.COM2),
-                   ("pi_out", po, N * kx * self.COM2), ("theta_out", to, N * ky * self.COM1)])
+        return self._check(fn, ty, N, m, n, shared, A=A, B=B, Gamma=Gamma, xcoms=xcoms, ycoms=ycoms, pi=pi,
+                           theta=theta, R=R, S=S, T=T, xcoms_out=xo, ycoms_out=yo, pi_out=po, theta_out=to)
 
     def _rerand_host(self, fn, shared, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T):
-        sh = self.shape(ty)
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        args = list(map(u8, (A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T)))
-        self._check_rerand(fn, ty, N, m, n, *args, shared=shared)
-        V = 1 if shared else N
-        xo, yo = self._out(V * m * self.COM1), self._out(V * n * self.COM2)
-        po, to = self._out(N * sh["kx"] * self.COM2), self._out(N * sh["ky"] * self.COM1)
+        args = list(map(_u8, (A, B, Gamma, xcoms, ycoms, pi, theta, R, S, T)))
+        want = self._check_rerand(fn, ty, N, m, n, *args, shared=shared)
+        xo, yo, po, to = (self._out(want[k]) for k in ("xcoms", "ycoms", "pi", "theta"))
         self._chk(getattr(self.lib, fn)(self.ctx, ty, ctypes.c_size_t(N), m, n, *[_p(a) for a in args], _p(xo), _p(yo),
                                         _p(po), _p(to)))
         return dict(xcoms=xo, ycoms=yo, pi=po, theta=to)
@@ -373,47 +365,31 @@ class Engine:
         return out.reshape(n, gsz)
 
     def verify_batch(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, ok=None):
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         if ok is None:
             ok = np.zeros(N, dtype=np.uint8)
         _need("gs_verify_batch", [("ok", ok, N)])
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
         self._check_verify("gs_verify_batch", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
-        self._chk(self.lib.gs_verify_batch(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(u8(A)), _p(u8(B)),
-                                           _p(u8(Gamma)), _p(u8(target)), _p(u8(xcoms)), _p(u8(ycoms)), _p(u8(pi)),
-                                           _p(u8(theta)), _p(ok)))
+        self._chk(self.lib.gs_verify_batch(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma), _p(target),
+                                           _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(ok)))
         return ok
 
     def prove_statement(self, ty, E, m, n, X, Y, A, B, Gamma, R, S, T, want_coms=True):
         """E equations of one type over the SAME variables X[m], Y[n] (commit randomness R, S): commitments once,
         one proof per equation (gs_prove_statement)."""
-        sh = self.shape(ty)
-        kx, ky, sx, sy = sh["kx"], sh["ky"], sh["sx"], sh["sy"]
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        X, Y, A, B, Gamma, R, S, T = map(u8, (X, Y, A, B, Gamma, R, S, T))
-        if not (0 <= ty <= 3) or m < 1 or n < 1:
-            raise GsError(1, "gs_prove_statement: bad equation type or empty variable list")
-        _need("gs_prove_statement", [("X", X, m * sx), ("Y", Y, n * sy), ("A", A, E * n * sx), ("B", B, E * m * sy),
-                                     ("Gamma", Gamma, E * m * n * self.FR), ("R", R, m * kx * self.FR),
-                                     ("S", S, n * ky * self.FR), ("T", T, E * ky * kx * self.FR)])
-        xc = self._out(m * self.COM1) if want_coms else None
-        yc = self._out(n * self.COM2) if want_coms else None
-        pi, th = self._out(E * kx * self.COM2), self._out(E * ky * self.COM1)
+        X, Y, A, B, Gamma, R, S, T = map(_u8, (X, Y, A, B, Gamma, R, S, T))
+        want = self._check("gs_prove_statement", ty, E, m, n, True, X=X, Y=Y, A=A, B=B, Gamma=Gamma, R=R, S=S, T=T)
+        xc = self._out(want["xcoms"]) if want_coms else None
+        yc = self._out(want["ycoms"]) if want_coms else None
+        pi, th = self._out(want["pi"]), self._out(want["theta"])
         self._chk(self.lib.gs_prove_statement(self.ctx, ty, ctypes.c_size_t(E), m, n, _p(X), _p(Y), _p(A), _p(B),
                                               _p(Gamma), _p(R), _p(S), _p(T), _p(xc), _p(yc), _p(pi), _p(th)))
         return dict(xcoms=xc, ycoms=yc, pi=pi, theta=th)
 
     def verify_statement(self, ty, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta):
-        sh = self.shape(ty)
-        kx, ky, sx, sy, st = sh["kx"], sh["ky"], sh["sx"], sh["sy"], sh["st"]
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
-        if not (0 <= ty <= 3) or m < 1 or n < 1:
-            raise GsError(1, "gs_verify_statement: bad equation type or empty variable list")
-        _need("gs_verify_statement", [("A", A, E * n * sx), ("B", B, E * m * sy), ("Gamma", Gamma, E * m * n * self.FR),
-                                      ("target", target, E * st), ("xcoms", xcoms, m * self.COM1),
-                                      ("ycoms", ycoms, n * self.COM2), ("pi", pi, E * kx * self.COM2),
-                                      ("theta", theta, E * ky * self.COM1)])
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        self._check("gs_verify_statement", ty, E, m, n, True, A=A, B=B, Gamma=Gamma, target=target, xcoms=xcoms,
+                    ycoms=ycoms, pi=pi, theta=theta)
         ok = np.zeros(E, dtype=np.uint8)
         self._chk(self.lib.gs_verify_statement(self.ctx, ty, ctypes.c_size_t(E), m, n, _p(A), _p(B), _p(Gamma),
                                                _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(ok)))
@@ -421,16 +397,15 @@ class Engine:
 
     def verify_batch_rlc(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
         """Batched verifier (host buffers).  rho: uint64[N*4].  Returns (ok_all, acc_pair_bytes)."""
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
         self._check_verify("gs_verify_batch_rlc", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
         _need("gs_verify_batch_rlc", [("rho", rho, 32 * N)])
         acc = self._out(2 * self.GT)
         ok = np.zeros(1, dtype=np.uint8)
-        self._chk(self.lib.gs_verify_batch_rlc(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(u8(A)), _p(u8(B)),
-                                               _p(u8(Gamma)), _p(u8(target)), _p(u8(xcoms)), _p(u8(ycoms)),
-                                               _p(u8(pi)), _p(u8(theta)), _p(rho), _p(acc), _p(ok)))
+        self._chk(self.lib.gs_verify_batch_rlc(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
+                                               _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho), _p(acc),
+                                               _p(ok)))
         return int(ok[0]), acc
 
     def gt_finalize_dev(self, accs_dev, count):
@@ -451,9 +426,8 @@ class Engine:
     def mat_left_mul(self, group, rows, k, lhs, col):
         fn = self.lib.gs_mat_left_mul_com1 if group == 1 else self.lib.gs_mat_left_mul_com2
         osz = self.COM1 if group == 1 else self.COM2
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         out = self._out(rows * osz)
-        lhs, col = u8(lhs), u8(col)
+        lhs, col = _u8(lhs), _u8(col)
         _need("gs_mat_left_mul", [("lhs", lhs, rows * k * self.FR), ("col", col, k * osz)])
         self._chk(fn(self.ctx, rows, k, _p(lhs), _p(col), _p(out)))
         return out.reshape(rows, osz)
@@ -462,18 +436,17 @@ class Engine:
         """Matrix<Fr> product (lists of rows of 4 x u64 Montgomery scalars) on the prover's preparation kernels."""
         rows, inner, cols = len(lhs), len(lhs[0]), len(rhs[0])
         assert len(rhs) == inner and all(len(r) == inner for r in lhs) and all(len(r) == cols for r in rhs)
-        u8 = lambda mat: np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.uint64).reshape(-1) for r in mat
+        pack = lambda mat: np.ascontiguousarray(np.stack([np.asarray(v, dtype=np.uint64).reshape(-1) for r in mat
                                                         for v in r])).view(np.uint8).reshape(-1)
         out = self._out(rows * cols * self.FR)
-        a, b = u8(lhs), u8(rhs)  # named: the buffers must outlive the call
+        a, b = pack(lhs), pack(rhs)  # named: the buffers must outlive the call
         self._chk(self.lib.gs_fr_matmul(self.ctx, rows, inner, cols, _p(a), _p(b), _p(out)))
         o = out.view(np.uint64).reshape(rows, cols, self.FR // 8)
         return [[o[i, j].copy() for j in range(cols)] for i in range(rows)]
 
     def pairing_sum(self, k, x, y):
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         out = self._out(4 * self.GT)
-        x, y = u8(x), u8(y)
+        x, y = _u8(x), _u8(y)
         _need("gs_pairing_sum", [("x", x, k * self.COM1), ("y", y, k * self.COM2)])
         self._chk(self.lib.gs_pairing_sum(self.ctx, k, _p(x), _p(y), _p(out)))
         return out.reshape(4, self.GT)
@@ -481,19 +454,17 @@ class Engine:
     def g_mul_batch(self, group, points, scalars, broadcast=False):
         fn = self.lib.gs_g1_mul_batch if group == 1 else self.lib.gs_g2_mul_batch
         gsz = self.G1 if group == 1 else self.G2
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        k = u8(scalars)
+        k = _u8(scalars)
         n = k.size // self.FR
         out = self._out(n * gsz)
-        points = u8(points)
+        points = _u8(points)
         _need("gs_g_mul_batch", [("points", points, (1 if broadcast else n) * gsz)])
         self._chk(fn(self.ctx, ctypes.c_size_t(n), _p(points), 1 if broadcast else 0, _p(k), _p(out)))
         return out.reshape(n, gsz)
 
     def multi_pairing_batch(self, n, k, P, Q):
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
         out = self._out(n * self.GT)
-        P, Q = u8(P), u8(Q)
+        P, Q = _u8(P), _u8(Q)
         _need("gs_multi_pairing_batch", [("P", P, n * k * self.G1), ("Q", Q, n * k * self.G2)])
         self._chk(self.lib.gs_multi_pairing_batch(self.ctx, ctypes.c_size_t(n), k, _p(P), _p(Q), _p(out)))
         return out.reshape(n, self.GT)
@@ -551,15 +522,6 @@ class Engine:
         self._chk(self.lib.gs_gt_pow_batch_dev(self.ctx, ctypes.c_size_t(n), _p(base), _p(k), _p(out)))
 
     # -- mixed batches / mixed-type Statements (gs_prove_mixed, gs_verify_mixed) -----------
-    def _part_sizes(self, ty, N, m, n, shared):
-        sh = self.shape(ty)
-        kx, ky, sx, sy, st = sh["kx"], sh["ky"], sh["sx"], sh["sy"], sh["st"]
-        V = 1 if shared else N
-        return dict(X=V * m * sx, Y=V * n * sy, A=N * n * sx, B=N * m * sy, Gamma=N * m * n * self.FR,
-                    R=V * m * kx * self.FR, S=V * n * ky * self.FR, T=N * ky * kx * self.FR, target=N * st,
-                    xcoms=V * m * self.COM1, ycoms=V * n * self.COM2, pi=N * kx * self.COM2, theta=N * ky * self.COM1,
-                    ok=N)
-
     def _parts(self, fn, parts, struct, in_keys, out_keys, dev):
         """parts: dicts with ty, N, m, n, the input arrays and (dev) the output arrays; host outputs are allocated
         here (xcoms / ycoms only when the part asks with want_coms, default True).  Every length is checked before a
@@ -570,9 +532,7 @@ class Engine:
         keep, outs = [], []
         for i, p in enumerate(parts):
             ty, N, m, n, shared = p["ty"], p["N"], p["m"], p["n"], bool(p.get("shared", False))
-            if not (0 <= ty <= 3) or m < 1 or n < 1:
-                raise GsError(1, "%s: bad equation type or empty variable list" % fn)
-            want = self._part_sizes(ty, N, m, n, shared)
+            want = self._check(fn, ty, N, m, n, shared)
             a = arr[i]
             a.equ_type, a.N, a.m, a.n, a.shared_vars = ty, N, m, n, 1 if shared else 0
             o = {}
@@ -745,6 +705,8 @@ class MultiEngine:
         self.COM1, self.COM2 = 2 * self.G1, 2 * self.G2
 
     shape = Engine.shape
+    _sizes = Engine._sizes
+    _check = Engine._check
     _check_prove = Engine._check_prove
     _check_verify = Engine._check_verify
 
@@ -832,21 +794,18 @@ class MultiEngine:
         self._chk(self.lib.gs_multi_set_crs(self.h, _p(crs)))
 
     def prove_batch(self, ty, N, m, n, X, Y, A, B, Gamma, R, S, T, want_coms=True):
-        sh = self.shape(ty)
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        X, Y, A, B, Gamma, R, S, T = map(u8, (X, Y, A, B, Gamma, R, S, T))
-        self._check_prove("gs_multi_prove_batch", ty, N, m, n, X, Y, A, B, Gamma, R, S, T)
-        z = lambda k: np.zeros(k, dtype=np.uint8)
-        xc = z(N * m * self.COM1) if want_coms else None
-        yc = z(N * n * self.COM2) if want_coms else None
-        pi, th = z(N * sh["kx"] * self.COM2), z(N * sh["ky"] * self.COM1)
+        X, Y, A, B, Gamma, R, S, T = map(_u8, (X, Y, A, B, Gamma, R, S, T))
+        want = self._check_prove("gs_multi_prove_batch", ty, N, m, n, X, Y, A, B, Gamma, R, S, T)
+        z = lambda k: np.zeros(want[k], dtype=np.uint8)
+        xc = z("xcoms") if want_coms else None
+        yc = z("ycoms") if want_coms else None
+        pi, th = z("pi"), z("theta")
         self._chk(self.lib.gs_multi_prove_batch(self.h, ty, ctypes.c_size_t(N), m, n, _p(X), _p(Y), _p(A), _p(B),
                                                 _p(Gamma), _p(R), _p(S), _p(T), _p(xc), _p(yc), _p(pi), _p(th)))
         return dict(xcoms=xc, ycoms=yc, pi=pi, theta=th)
 
     def verify_batch(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta):
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
         self._check_verify("gs_multi_verify_batch", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
         ok = np.zeros(N, dtype=np.uint8)
         self._chk(self.lib.gs_multi_verify_batch(self.h, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
@@ -855,8 +814,7 @@ class MultiEngine:
 
     def verify_batch_rlc(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
         """-> (ok_all, the ndev gathered accumulator pairs as bytes)"""
-        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
         self._check_verify("gs_multi_verify_batch_rlc", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
         rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
         _need("gs_multi_verify_batch_rlc", [("rho", rho, 32 * N)])

@@ -29,6 +29,7 @@
 #include "gs_params_bls12_381.h"
 #include "gs_params_bn254.h"
 #include "gs_kernels.cuh"
+#include "gs_layout.h"
 
 namespace gs {
 GS_ZERO_ONE(Bls12_381)
@@ -184,7 +185,7 @@ static int ensure(gs_ctx* c, DevBuf& b, size_t bytes) {
   if (b.p) {  // growing: kernels already enqueued may still read the old buffer
     if (c && c->rec) {
       // recording: nothing has been launched, a sync protects nothing -- the launches that will read the old buffer
-      // are in the recorder.  Park it; mixed_run / mixed_host release the list after the replay.
+      // are in the recorder.  Park it; mixed_dev / mixed_host release the list after the replay.
       c->deferred_free.push_back(b.p);
     } else {
       if (c) {
@@ -870,8 +871,9 @@ static int replay(gs_ctx* c, Recorder& R) {
 // ---------------------------------------------------------------------------
 // scalar preparation goes one-lane-per-output once an equation carries this many Gamma entries
 static inline bool wide_prep(int m, int n) { return (long)m * n >= 1024; }
-static inline bool x_is_group(int ty) { return ty == GS_PPE || ty == GS_MSMEG1; }
-static inline bool y_is_group(int ty) { return ty == GS_PPE || ty == GS_MSMEG2; }
+namespace lay = gs_layout;  // the sizes of a batch's arrays (gs_layout.h)
+using lay::x_is_group;
+using lay::y_is_group;
 
 template <class C> struct Sz {
   // BOUNDARY sizes (include/gs_amd.h), not the internal radix-2^28 structs
@@ -1332,8 +1334,7 @@ template <class C, class F> static int run_red(gs_ctx* c, size_t N, const RedLau
 template <class C, class F>
 static int run_side(gs_ctx* c, const char* tag, size_t N, SidePlan& sp, const ArrTab& arrs, const Fr<C>* pool,
                     int pool_n, const Aff<F>* tab, const OutTab& outs, hipStream_t vstream = nullptr,
-                    hipEvent_t vev0 = nullptr, hipEvent_t vev1 = nullptr, RedLaunch* defer = nullptr,
-                    const unsigned* pipe_masks = nullptr) {
+                    hipEvent_t vev0 = nullptr, hipEvent_t vev1 = nullptr, const unsigned* pipe_masks = nullptr) {
   // pipe_masks (host-pointer calls): {inputs the fixed-base kernel reads, inputs the variable-base kernel reads,
   // outputs complete after the commitments' reduction, outputs complete after the side's last reduction}
   std::string t(tag);
@@ -1362,7 +1363,7 @@ static int run_side(gs_ctx* c, const char* tag, size_t N, SidePlan& sp, const Ar
   // host-pointer calls: the commitments depend on the fixed-base kernel alone -- reduce them now and send them back
   // across PCIe under the variable-base kernel
   // (from 2^14 equations on: below that the extra launch and events cost more than the copy they hide)
-  const bool early = c->pipe && pipe_masks && !c->rec && !fork && !defer && sp.ncom > 0 && sp.ncom < (int)sp.red.size() &&
+  const bool early = c->pipe && pipe_masks && !c->rec && !fork && sp.ncom > 0 && sp.ncom < (int)sp.red.size() &&
                      N >= 16 * c->simd_slots;
   if (early) {
     RedLaunch rc0;
@@ -1474,10 +1475,6 @@ static int run_side(gs_ctx* c, const char* tag, size_t N, SidePlan& sp, const Ar
   r.nred = r.hred.size();
   r.nslots = sp.nslots;
   r.outs = outs;
-  if (defer) {
-    *defer = r;
-    return GS_OK;
-  }
   RC((run_red<C, F>(c, N, r)));
   if (pipe_masks) RC(out_ready(c, pipe_masks[2] | pipe_masks[3]));
   return GS_OK;
@@ -1637,16 +1634,10 @@ template <class C> struct Impl {
       hipEventRecord(c->sev[0], c->stream);
       hipStreamWaitEvent(c->side[0], c->sev[0], 0);
     }
-    // larger batches: only the two reduction kernels (one inversion chain per lane, a few hundred waves each) run
-    // side by side, after both sides' partial sums are complete
-    // (not for a host-pointer call: there the G1 side's outputs go back across PCIe under the G2 side's kernels)
-    // (round 3: OFF.  A side stream is another hardware queue with its own private-segment reservation; two of them
-    // holding a few hundred MB each is what starved the main queue's big kernels of scratch waves later in the
-    // process -- profiles/r3/scratch_pool.txt.  The 1-2 % it gained at 2^12..2^16 are not worth a 4x cliff.)
-    const bool pair_reds = false;
-    RedLaunch red1, red2;
+    // (larger batches once ran the two sides' reduction kernels side by side on a second stream: +1-2 % at 2^12..2^16,
+    // but the extra queue's scratch reservation cost later big kernels 4x -- profiles/r3/scratch_pool.txt.  Removed.)
     // G1 side: xcoms (m) + theta (ky).  constants A (len n) multiply S; Phi multiplies X; fixed part T.
-    auto side_g1 = [&](bool first) -> int {
+    auto side_g1 = [&]() -> int {
       SidePlan sp;
       sp.tm = xg ? pick_tm(c, fillN(c, N), m + n, ky, false, ky) : 1;
       build_side(sp, xcoms != nullptr, m, n, xg, kx, ky, pm.RC, pm.XC, pm.SC, pm.PHI, pm.TC, pm.SIG);
@@ -1668,12 +1659,11 @@ template <class C> struct Impl {
       // (the fixed-base kernel reads X as the commitments' affine addend; the constants A only feed the variable-base one)
       const unsigned masks[4] = {BIT(PI_X), BIT(PI_A), BIT(PO_XC), BIT(PO_TH)};
       RC((run_side<C, F1>(c, ".g1", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs,
-                          ov ? c->side[1] : nullptr, c->sev[1], c->sev[2], pair_reds ? &red1 : nullptr, masks)));
-      (void)first;
+                          ov ? c->side[1] : nullptr, c->sev[1], c->sev[2], masks)));
       return GS_OK;
     };
     // G2 side: ycoms (n) + pi (kx).  constants B (len m) multiply R; Psi multiplies Y; fixed part Omega.
-    auto side_g2 = [&](bool first) -> int {
+    auto side_g2 = [&]() -> int {
       SidePlan sp;
       sp.tm = yg ? pick_tm(c, fillN(c, N), m + n, kx, true, kx) : 1;
       build_side(sp, ycoms != nullptr, n, m, yg, ky, kx, pm.SC, pm.YC, pm.RC, pm.PSI, pm.OM, pm.RHO);
@@ -1695,34 +1685,23 @@ template <class C> struct Impl {
       RangeGuard rg("gs.prove.g2");
       const unsigned masks[4] = {BIT(PI_Y), BIT(PI_B), BIT(PO_YC), BIT(PO_PI)};
       RC((run_side<C, F2>(c, ".g2", N, sp, arrs, (const S*)pool, pm.total, (const A2*)c->tabs->tab16_g2.p, outs,
-                          ov ? c->side[2] : nullptr, c->sev[3], c->sev[4], pair_reds ? &red2 : nullptr, masks)));
+                          ov ? c->side[2] : nullptr, c->sev[3], c->sev[4], masks)));
       if (ov) {
         hipEventRecord(c->sev[5], c->side[0]);
         c->cur = nullptr;
         hipStreamWaitEvent(c->stream, c->sev[5], 0);
       }
-      (void)first;
       return GS_OK;
     };
     // A host-pointer call runs the G2 side FIRST: every output but the last proof element crosses PCIe under later
     // kernels (the commitments of a side under its variable-base kernel, the first side's proof element under the second
     // side), and the one that is left after the last kernel is then theta (1/8 of the output bytes) rather than pi.
     if (c->pipe && !ov && N >= 16 * c->simd_slots) {
-      RC(side_g2(true));
-      RC(side_g1(false));
+      RC(side_g2());
+      RC(side_g1());
     } else {
-      RC(side_g1(true));
-      RC(side_g2(false));
-    }
-    if (pair_reds) {
-      hipEventRecord(c->sev[0], c->stream);  // every partial sum of both sides is enqueued before this point
-      hipStreamWaitEvent(c->side[0], c->sev[0], 0);
-      c->cur = c->side[0];
-      RC((run_red<C, F2>(c, N, red2)));
-      hipEventRecord(c->sev[5], c->side[0]);
-      c->cur = nullptr;
-      RC((run_red<C, F1>(c, N, red1)));
-      hipStreamWaitEvent(c->stream, c->sev[5], 0);
+      RC(side_g1());
+      RC(side_g2());
     }
     return GS_OK;
   }
@@ -1793,7 +1772,7 @@ template <class C> struct Impl {
                                  proofs ? BIT(g2 ? RO_PI : RO_TH) : 0u};
       const void* tab = g2 ? c->tabs->tab16_g2.p : c->tabs->tab16_g1.p;
       return run_side<C, F>(c, tag, NN, sp, arrs, (const S*)pool, pm.total, (const Aff<F>*)tab, outs, nullptr, nullptr,
-                            nullptr, nullptr, masks);
+                            nullptr, masks);
     };
     if (shared) {  // the Statement's commitments once (equation 0 of the pool holds R', S'), then the E proofs
       RC(side((F1*)nullptr, 1, true, false, ".rc1"));
@@ -3028,132 +3007,177 @@ COMMIT_HOST(gs_commit_g2, gs_commit_g2_dev, 4 * fq, 2, 8 * fq)
 COMMIT_HOST(gs_commit_fr_b1, gs_commit_fr_b1_dev, SZ_FR, 1, 4 * fq)
 COMMIT_HOST(gs_commit_fr_b2, gs_commit_fr_b2_dev, SZ_FR, 1, 8 * fq)
 
-// ---- prove -------------------------------------------------------------------
+// ---- prove / verify / rerandomize: shared plumbing ------------------------------------------------------------
 static int check_shape(gs_ctx* c, int ty, int m, int n) {
   if (ty < 0 || ty > 3) return fail(c, GS_ERR_ARG, "bad equation type");
   // the reference indexes rand[0] / gamma[0]: empty variable lists panic (prove.rs:106-113)
   if (m < 1 || n < 1) return fail(c, GS_ERR_SHAPE, "m and n must be >= 1 (reference asserts, prove.rs:106-113)");
-  if (m > 4096 || n > 4096 || (long)m * n > (1L << 22)) return fail(c, GS_ERR_SHAPE, "shape too large for task tables");
+  if (!lay::shape_fits(m, n)) return fail(c, GS_ERR_SHAPE, "shape too large for task tables");
   return GS_OK;
 }
 
-int gs_prove_batch_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A,
-                       const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
-                       void* ycoms, void* pi, void* theta) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (N == 0) return GS_OK;
-  if (!X || !Y || !A || !B || !G || !R || !S || !T || !pi || !theta) return fail(c, GS_ERR_ARG, "null pointer");
-  return DISPATCH(c, prove(c, ty, N, m, n, X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta));
-}
-
-// host-pointer prove in three phases so that a mixed call can interleave several sub-batches: stage (the workers start
-// copying), run (kernels enqueued behind per-array upload events), finish (outputs back, stream drained)
-struct ProveArgs {
+// One homogeneous batch of any of the three operations.  p[] is indexed by the operation's HostPipe slot (PI_* / VI_*
+// / RI_*): host pointers at the un-suffixed entry points, device pointers at the _dev ones and inside.
+struct BatchArgs {
   int ty;
   size_t N;
   int m, n;
-  const void *X, *Y, *A, *B, *G, *R, *S, *T;
-  void *xcoms, *ycoms, *pi, *theta;
-  bool shared;  // a Statement's part: ONE copy of X, Y, R, S and of the commitments for all N equations
+  bool shared;  // a Statement('s part): ONE copy of X, Y, R, S and of the commitments for all N equations
+  const void* p[14];
+  void* out(int slot) const { return const_cast<void*>(p[slot]); }
 };
-static int prove_host_stage(gs_ctx* c, const ProveArgs& a, HostPipe& hp, size_t base = 0, bool start = true) {
-  size_t fq = sz_fq(c->curve), N = a.N;
-  bool xg = x_is_group(a.ty), yg = y_is_group(a.ty);
-  int kx = xg ? 2 : 1, ky = yg ? 2 : 1, m = a.m, n = a.n;
-  size_t sx = xg ? 2 * fq : SZ_FR, sy = yg ? 4 * fq : SZ_FR;
-  const size_t V = a.shared ? 1 : N;
-  hp.in(PI_X, a.X, V * m * sx);
-  hp.in(PI_Y, a.Y, V * n * sy);
-  hp.in(PI_A, a.A, N * n * sx);
-  hp.in(PI_B, a.B, N * m * sy);
-  hp.in(PI_G, a.G, N * m * n * SZ_FR);
-  hp.in(PI_R, a.R, V * m * kx * SZ_FR);
-  hp.in(PI_S, a.S, V * n * ky * SZ_FR);
-  hp.in(PI_T, a.T, N * ky * kx * SZ_FR);
-  hp.out(PO_XC, a.xcoms, V * m * 4 * fq);
-  hp.out(PO_YC, a.ycoms, V * n * 8 * fq);
-  hp.out(PO_PI, a.pi, N * kx * 8 * fq);
-  hp.out(PO_TH, a.theta, N * ky * 4 * fq);
+// An operation states its arrays ONCE: HostPipe slot (= index into BatchArgs::p), which entry of the layout table
+// gives its bytes, direction, and whether the pointer may be NULL.  The null check, the staging of a host-pointer call
+// and the overlap check all walk this list.
+enum { ARR_IN = 0, ARR_OUT = 1, ARR_OPT = 2 };
+struct ArrDesc {
+  int slot;
+  lay::Array arr;
+  int flags;
+};
+struct Op {
+  const ArrDesc* arrs;
+  int narrs;
+  const int* (*order)(int ty);  // host-pointer calls: the order in which the inputs are staged
+  int norder;
+  int (*run)(gs_ctx*, const BatchArgs&);  // the kernels of a checked, non-empty batch (device pointers)
+};
+static lay::Layout layout_of(const gs_ctx* c, const BatchArgs& a) {
+  return lay::Layout(sz_fq(c->curve), a.ty, a.N, a.m, a.n, a.shared);
+}
+static int batch_check(gs_ctx* c, const Op& op, const BatchArgs& a) {
+  RC(check_ctx(c, true));
+  RC(check_shape(c, a.ty, a.m, a.n));
+  if (a.N == 0) return GS_OK;
+  for (int i = 0; i < op.narrs; i++)
+    if (!(op.arrs[i].flags & ARR_OPT) && !a.p[op.arrs[i].slot]) return fail(c, GS_ERR_ARG, "null pointer");
+  return GS_OK;
+}
+static int batch_dev(gs_ctx* c, const Op& op, const BatchArgs& a) {
+  RC(batch_check(c, op, a));
+  return a.N == 0 ? (int)GS_OK : op.run(c, a);
+}
+// A host-pointer call runs in three phases so that a mixed call can interleave several sub-batches: stage (the arrays
+// are declared, the workers start copying), run (kernels enqueued behind per-array upload events), HostPipe::finish
+// (outputs back, stream drained).
+static int batch_stage(gs_ctx* c, const Op& op, const BatchArgs& a, HostPipe& hp, size_t base, bool start) {
+  const lay::Layout L = layout_of(c, a);
+  for (int i = 0; i < op.narrs; i++) {
+    const ArrDesc& d = op.arrs[i];
+    if (d.flags & ARR_OUT)
+      hp.out(d.slot, a.out(d.slot), L.bytes[d.arr]);
+    else
+      hp.in(d.slot, a.p[d.slot], L.bytes[d.arr]);
+  }
+  return start ? hp.begin(op.order(a.ty), op.norder, base, base == 0) : (int)GS_OK;
+}
+static int batch_run_staged(gs_ctx* c, const Op& op, const BatchArgs& a, const HostPipe& hp) {
+  BatchArgs d = a;
+  for (int i = 0; i < op.narrs; i++) d.p[op.arrs[i].slot] = hp.dev(op.arrs[i].slot);
+  return op.run(c, d);
+}
+static int batch_host_checked(gs_ctx* c, const Op& op, const BatchArgs& a) {
+  HostPipe hp(c);
+  RC(batch_stage(c, op, a, hp, 0, true));
+  RC(batch_run_staged(c, op, a, hp));
+  return hp.finish();
+}
+static int batch_host(gs_ctx* c, const Op& op, const BatchArgs& a) {
+  RC(batch_check(c, op, a));
+  return a.N == 0 ? (int)GS_OK : batch_host_checked(c, op, a);
+}
+
+// ---- prove -------------------------------------------------------------------
+static const ArrDesc kProveArrs[] = {
+    {PI_X, lay::X, ARR_IN},      {PI_Y, lay::Y, ARR_IN},      {PI_A, lay::A, ARR_IN},
+    {PI_B, lay::B, ARR_IN},      {PI_G, lay::GAMMA, ARR_IN},  {PI_R, lay::R, ARR_IN},
+    {PI_S, lay::S, ARR_IN},      {PI_T, lay::T, ARR_IN},      {PO_XC, lay::XCOMS, ARR_OUT | ARR_OPT},
+    {PO_YC, lay::YCOMS, ARR_OUT | ARR_OPT}, {PO_PI, lay::PI, ARR_OUT}, {PO_TH, lay::THETA, ARR_OUT}};
+static const int* prove_order(int) {
   // staging order = the order prove() asks for them (scalars, then the G2 side's arguments, then the G1 side's)
   static const int order[] = {PI_G, PI_R, PI_S, PI_T, PI_Y, PI_B, PI_X, PI_A};  // (Y before B: the fixed-base kernel reads Y)
-  return start ? hp.begin(order, 8, base, base == 0) : (int)GS_OK;
+  return order;
 }
-static int prove_host_run(gs_ctx* c, const ProveArgs& a, HostPipe& hp) {
-  return (a.shared ? gs_prove_statement_dev : gs_prove_batch_dev)(c, a.ty, a.N, a.m, a.n, hp.dev(PI_X), hp.dev(PI_Y), hp.dev(PI_A), hp.dev(PI_B), hp.dev(PI_G),
-                            hp.dev(PI_R), hp.dev(PI_S), hp.dev(PI_T), hp.dev(PO_XC), hp.dev(PO_YC), hp.dev(PO_PI),
-                            hp.dev(PO_TH));
+static int prove_run(gs_ctx* c, const BatchArgs& a) {
+  const void* const* p = a.p;
+  void *xcoms = a.out(PO_XC), *ycoms = a.out(PO_YC);
+  if (a.shared) {
+    // a Statement: the commitments, once (commit.rs:78-100,125-156,178-200,225-256); the prover then writes none
+    RC(need(c, BIT(PI_X) | BIT(PI_Y) | BIT(PI_R) | BIT(PI_S)));
+    if (xcoms) RC((lay::x_is_group(a.ty) ? gs_commit_g1_dev : gs_commit_fr_b1_dev)(c, (size_t)a.m, p[PI_X], p[PI_R], xcoms));
+    if (ycoms) RC((lay::y_is_group(a.ty) ? gs_commit_g2_dev : gs_commit_fr_b2_dev)(c, (size_t)a.n, p[PI_Y], p[PI_S], ycoms));
+    xcoms = ycoms = nullptr;
+  }
+  return DISPATCH(c, prove(c, a.ty, a.N, a.m, a.n, p[PI_X], p[PI_Y], p[PI_A], p[PI_B], p[PI_G], p[PI_R], p[PI_S],
+                           p[PI_T], xcoms, ycoms, a.out(PO_PI), a.out(PO_TH), a.shared));
+}
+static const Op kProve = {kProveArrs, sizeof kProveArrs / sizeof *kProveArrs, prove_order, 8, prove_run};
+static BatchArgs from_part(const gs_prove_part& p) {
+  return BatchArgs{p.equ_type, p.N, p.m, p.n, p.shared_vars != 0,
+                   {p.X, p.Y, p.A, p.B, p.Gamma, p.R, p.S, p.T, p.xcoms, p.ycoms, p.pi, p.theta}};
+}
+int gs_prove_batch_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                       const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
+                       void* ycoms, void* pi, void* theta) {
+  return batch_dev(c, kProve, {ty, N, m, n, false, {X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta}});
 }
 int gs_prove_batch(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A,
                    const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
                    void* ycoms, void* pi, void* theta) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (N == 0) return GS_OK;
-  if (!X || !Y || !A || !B || !G || !R || !S || !T || !pi || !theta) return fail(c, GS_ERR_ARG, "null pointer");
-  ProveArgs a{ty, N, m, n, X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta, false};
-  HostPipe hp(c);
-  RC(prove_host_stage(c, a, hp));
-  RC(prove_host_run(c, a, hp));
-  return hp.finish();
+  return batch_host(c, kProve, {ty, N, m, n, false, {X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta}});
+}
+// Statement: E equations of one type over the SAME committed variables (statement.rs:24-28,109)
+int gs_prove_statement_dev(gs_ctx* c, int ty, size_t E, int m, int n, const void* X, const void* Y, const void* A,
+                           const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
+                           void* ycoms, void* pi, void* theta) {
+  return batch_dev(c, kProve, {ty, E, m, n, true, {X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta}});
+}
+int gs_prove_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* X, const void* Y, const void* A,
+                       const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
+                       void* ycoms, void* pi, void* theta) {
+  return batch_host(c, kProve, {ty, E, m, n, true, {X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta}});
 }
 
 // ---- verify ------------------------------------------------------------------
-int gs_verify_batch_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                        uint8_t* ok) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (N == 0) return GS_OK;
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  return DISPATCH(c, verify(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, ok));
-}
-
-struct VerifyArgs {
-  int ty;
-  size_t N;
-  int m, n;
-  const void *A, *B, *G, *target, *xcoms, *ycoms, *pi, *theta;
-  uint8_t* ok;
-  bool shared;
-};
-static int verify_host_stage(gs_ctx* c, const VerifyArgs& a, HostPipe& hp, size_t base = 0, bool start = true) {
-  size_t fq = sz_fq(c->curve), N = a.N;
-  int ty = a.ty, m = a.m, n = a.n;
-  bool xg = x_is_group(ty), yg = y_is_group(ty);
-  int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
-  size_t sx = xg ? 2 * fq : SZ_FR, sy = yg ? 4 * fq : SZ_FR;
-  size_t st_ = ty == GS_PPE ? 12 * fq : ty == GS_MSMEG1 ? 2 * fq : ty == GS_MSMEG2 ? 4 * fq : SZ_FR;
-  hp.in(VI_A, a.A, N * n * sx);
-  hp.in(VI_B, a.B, N * m * sy);
-  hp.in(VI_G, a.G, N * m * n * SZ_FR);
-  hp.in(VI_TG, a.target, N * st_);
-  hp.in(VI_XC, a.xcoms, (a.shared ? 1 : N) * m * 4 * fq);
-  hp.in(VI_YC, a.ycoms, (a.shared ? 1 : N) * n * 8 * fq);
-  hp.in(VI_PI, a.pi, N * kx * 8 * fq);
-  hp.in(VI_TH, a.theta, N * ky * 4 * fq);
-  hp.out(VO_OK, a.ok, N);
+static const ArrDesc kVerifyArrs[] = {
+    {VI_A, lay::A, ARR_IN},      {VI_B, lay::B, ARR_IN},      {VI_G, lay::GAMMA, ARR_IN},
+    {VI_TG, lay::TARGET, ARR_IN}, {VI_XC, lay::XCOMS, ARR_IN}, {VI_YC, lay::YCOMS, ARR_IN},
+    {VI_PI, lay::PI, ARR_IN},    {VI_TH, lay::THETA, ARR_IN}, {VO_OK, lay::OK, ARR_OUT}};
+static const int* verify_order(int ty) {
   // Gamma and the G1-side arguments first (the verifier's Gamma-MSM runs under the upload of the rest)
   static const int order_g[] = {VI_G, VI_A, VI_XC, VI_TG, VI_B, VI_YC, VI_PI, VI_TH};
   static const int order_s[] = {VI_G, VI_A, VI_B, VI_TG, VI_XC, VI_YC, VI_PI, VI_TH};
-  return start ? hp.begin(ty == GS_PPE || ty == GS_MSMEG2 ? order_g : order_s, 8, base, base == 0) : (int)GS_OK;
+  return ty == GS_PPE || ty == GS_MSMEG2 ? order_g : order_s;
 }
-static int verify_host_run(gs_ctx* c, const VerifyArgs& a, HostPipe& hp) {
-  return (a.shared ? gs_verify_statement_dev : gs_verify_batch_dev)(c, a.ty, a.N, a.m, a.n, hp.dev(VI_A), hp.dev(VI_B), hp.dev(VI_G), hp.dev(VI_TG),
-                             hp.dev(VI_XC), hp.dev(VI_YC), hp.dev(VI_PI), hp.dev(VI_TH), (uint8_t*)hp.dev(VO_OK));
+static int verify_run(gs_ctx* c, const BatchArgs& a) {
+  const void* const* p = a.p;
+  return DISPATCH(c, verify(c, a.ty, a.N, a.m, a.n, p[VI_A], p[VI_B], p[VI_G], p[VI_TG], p[VI_XC], p[VI_YC], p[VI_PI],
+                            p[VI_TH], (uint8_t*)a.out(VO_OK), a.shared));
+}
+static const Op kVerify = {kVerifyArrs, sizeof kVerifyArrs / sizeof *kVerifyArrs, verify_order, 8, verify_run};
+static BatchArgs from_part(const gs_verify_part& p) {
+  return BatchArgs{p.equ_type, p.N, p.m, p.n, p.shared_vars != 0,
+                   {p.A, p.B, p.Gamma, p.target, p.xcoms, p.ycoms, p.pi, p.theta, p.ok}};
+}
+int gs_verify_batch_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                        uint8_t* ok) {
+  return batch_dev(c, kVerify, {ty, N, m, n, false, {A, B, G, target, xcoms, ycoms, pi, theta, ok}});
 }
 int gs_verify_batch(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                     const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
                     uint8_t* ok) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (N == 0) return GS_OK;
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  VerifyArgs a{ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, ok, false};
-  HostPipe hp(c);
-  RC(verify_host_stage(c, a, hp));
-  RC(verify_host_run(c, a, hp));
-  return hp.finish();
+  return batch_host(c, kVerify, {ty, N, m, n, false, {A, B, G, target, xcoms, ycoms, pi, theta, ok}});
+}
+int gs_verify_statement_dev(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
+                            const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                            const void* theta, uint8_t* ok) {
+  return batch_dev(c, kVerify, {ty, E, m, n, true, {A, B, G, target, xcoms, ycoms, pi, theta, ok}});
+}
+int gs_verify_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
+                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                        uint8_t* ok) {
+  return batch_host(c, kVerify, {ty, E, m, n, true, {A, B, G, target, xcoms, ycoms, pi, theta, ok}});
 }
 
 // ---- mixed batches: several sub-batches (any types and shapes) in ONE call ----------------------------------------
@@ -3185,9 +3209,24 @@ static int release_deferred(gs_ctx* c, int rc) {
   return rc;
 }
 extern "C++" {
-template <class FN> static int mixed_run(gs_ctx* c, int nparts, size_t total_n, FN part_fn) {
+template <class PART> static std::vector<BatchArgs> parts_of(const PART* p, int nparts) {
+  std::vector<BatchArgs> a;
+  for (int i = 0; i < nparts; i++) a.push_back(from_part(p[i]));
+  return a;
+}
+}  // extern "C++"
+static int check_parts(gs_ctx* c, int nparts, const void* p, const char* what) {
+  RC(check_ctx(c, true));
+  if (nparts < 0 || nparts > GS_MIXED_MAX || (nparts && !p)) return fail(c, GS_ERR_ARG, what);
+  return GS_OK;
+}
+// device pointers: every part is checked as its turn comes (a failed part: nothing was launched when merging)
+static int mixed_dev(gs_ctx* c, const Op& op, const std::vector<BatchArgs>& a) {
+  const int nparts = (int)a.size();
+  size_t total_n = 0;
+  for (const BatchArgs& p : a) total_n += p.N;
   if (nparts <= 1 || c->rec || !merge_parts(c, total_n)) {
-    for (int i = 0; i < nparts; i++) RC(part_fn(i));
+    for (int i = 0; i < nparts; i++) RC(batch_dev(c, op, a[i]));
     return GS_OK;
   }
   Recorder R;
@@ -3198,7 +3237,7 @@ template <class FN> static int mixed_run(gs_ctx* c, int nparts, size_t total_n, 
   for (int i = 0; i < nparts && rc == GS_OK; i++) {
     R.cur = i;
     c->scratch_tag = i + 1;
-    rc = part_fn(i);
+    rc = batch_dev(c, op, a[i]);
   }
   c->rec = nullptr;
   c->fill_n = 0;
@@ -3206,44 +3245,21 @@ template <class FN> static int mixed_run(gs_ctx* c, int nparts, size_t total_n, 
   if (rc == GS_OK) rc = replay(c, R);  // (a failed part: nothing was launched)
   return release_deferred(c, rc);
 }
-}  // extern "C++"
-int gs_prove_mixed_dev(gs_ctx* c, int nparts, const gs_prove_part* p) {
-  RC(check_ctx(c, true));
-  if (nparts < 0 || nparts > GS_MIXED_MAX || (nparts && !p)) return fail(c, GS_ERR_ARG, "gs_prove_mixed: 0..8 parts");
-  RangeGuard rg("gs.prove_mixed");
-  size_t tot = 0;
-  for (int i = 0; i < nparts; i++) tot += p[i].N;
-  return mixed_run(c, nparts, tot, [&](int i) {
-    return (p[i].shared_vars ? gs_prove_statement_dev : gs_prove_batch_dev)(
-        c, p[i].equ_type, p[i].N, p[i].m, p[i].n, p[i].X, p[i].Y, p[i].A, p[i].B, p[i].Gamma, p[i].R, p[i].S, p[i].T,
-        p[i].xcoms, p[i].ycoms, p[i].pi, p[i].theta);
-  });
-}
-int gs_verify_mixed_dev(gs_ctx* c, int nparts, const gs_verify_part* p) {
-  RC(check_ctx(c, true));
-  if (nparts < 0 || nparts > GS_MIXED_MAX || (nparts && !p)) return fail(c, GS_ERR_ARG, "gs_verify_mixed: 0..8 parts");
-  RangeGuard rg("gs.verify_mixed");
-  size_t tot = 0;
-  for (int i = 0; i < nparts; i++) tot += p[i].N;
-  return mixed_run(c, nparts, tot, [&](int i) {
-    return (p[i].shared_vars ? gs_verify_statement_dev : gs_verify_batch_dev)(
-        c, p[i].equ_type, p[i].N, p[i].m, p[i].n, p[i].A, p[i].B, p[i].Gamma, p[i].target, p[i].xcoms, p[i].ycoms,
-        p[i].pi, p[i].theta, p[i].ok);
-  });
-}
 // host pointers: every part is staged into its own region of the pinned buffer (the memcpy workers start at once), the
 // parts' launches are recorded behind their upload events and replayed merged, then the outputs come back
-extern "C++" {
-template <class ARGS, class STAGE, class RUN>
-static int mixed_host(gs_ctx* c, std::vector<ARGS>& a, size_t total_n, STAGE stage, RUN run) {
+static int mixed_host(gs_ctx* c, const Op& op, const std::vector<BatchArgs>& parts, const char* range) {
+  std::vector<BatchArgs> a;  // every part's shape and pointers are checked first; empty parts then drop out
+  size_t total_n = 0;
+  for (const BatchArgs& p : parts) {
+    RC(batch_check(c, op, p));
+    if (p.N == 0) continue;
+    a.push_back(p);
+    total_n += p.N;
+  }
+  RangeGuard rg(range);
   const int np = (int)a.size();
   if (np <= 1 || !merge_parts(c, total_n)) {
-    for (int i = 0; i < np; i++) {
-      HostPipe h(c);
-      RC(stage(c, a[i], h, (size_t)0, true));
-      RC(run(c, a[i], h));
-      RC(h.finish());
-    }
+    for (int i = 0; i < np; i++) RC(batch_host_checked(c, op, a[i]));
     return GS_OK;
   }
   std::vector<std::unique_ptr<HostPipe>> hp;
@@ -3253,7 +3269,7 @@ static int mixed_host(gs_ctx* c, std::vector<ARGS>& a, size_t total_n, STAGE sta
   for (int i = 0; i < np; i++) {
     hp.emplace_back(new HostPipe(c));
     base[i] = need_pin;
-    need_pin += stage(c, a[i], *hp[i], (size_t)0, false) == GS_OK ? hp[i]->layout() : 0;
+    need_pin += batch_stage(c, op, a[i], *hp[i], 0, false) == GS_OK ? hp[i]->layout() : 0;
   }
   hp.clear();
   c->pipe = nullptr;
@@ -3263,7 +3279,7 @@ static int mixed_host(gs_ctx* c, std::vector<ARGS>& a, size_t total_n, STAGE sta
   for (int i = 0; i < np && rc == GS_OK; i++) {
     hp.emplace_back(new HostPipe(c));
     c->scratch_tag = i + 1;
-    rc = stage(c, a[i], *hp[i], base[i], true);
+    rc = batch_stage(c, op, a[i], *hp[i], base[i], true);
   }
   // 3. record the parts' launches (their need() calls enqueue the uploads and make the stream wait), replay merged
   Recorder R;
@@ -3274,7 +3290,7 @@ static int mixed_host(gs_ctx* c, std::vector<ARGS>& a, size_t total_n, STAGE sta
     R.cur = i;
     c->scratch_tag = i + 1;
     c->pipe = hp[i].get();
-    rc = run(c, a[i], *hp[i]);
+    rc = batch_run_staged(c, op, a[i], *hp[i]);
   }
   c->rec = nullptr;
   c->fill_n = 0;
@@ -3292,180 +3308,93 @@ static int mixed_host(gs_ctx* c, std::vector<ARGS>& a, size_t total_n, STAGE sta
   if (rc != GS_OK) drain_ctx(c);  // uploads / downloads of the parts that did start (not only c->stream)
   return release_deferred(c, rc);
 }
-}  // extern "C++"
-int gs_prove_mixed(gs_ctx* c, int nparts, const gs_prove_part* p) {
-  RC(check_ctx(c, true));
-  if (nparts < 0 || nparts > GS_MIXED_MAX || (nparts && !p)) return fail(c, GS_ERR_ARG, "gs_prove_mixed: 0..8 parts");
-  std::vector<ProveArgs> a;
-  size_t tot = 0;
-  for (int i = 0; i < nparts; i++) {
-    RC(check_shape(c, p[i].equ_type, p[i].m, p[i].n));
-    if (p[i].N == 0) continue;
-    if (!p[i].X || !p[i].Y || !p[i].A || !p[i].B || !p[i].Gamma || !p[i].R || !p[i].S || !p[i].T || !p[i].pi || !p[i].theta)
-      return fail(c, GS_ERR_ARG, "null pointer");
-    a.push_back(ProveArgs{p[i].equ_type, p[i].N, p[i].m, p[i].n, p[i].X, p[i].Y, p[i].A, p[i].B, p[i].Gamma, p[i].R,
-                          p[i].S, p[i].T, p[i].xcoms, p[i].ycoms, p[i].pi, p[i].theta, p[i].shared_vars != 0});
-    tot += p[i].N;
-  }
+int gs_prove_mixed_dev(gs_ctx* c, int nparts, const gs_prove_part* p) {
+  RC(check_parts(c, nparts, p, "gs_prove_mixed: 0..8 parts"));
   RangeGuard rg("gs.prove_mixed");
-  return mixed_host(c, a, tot, prove_host_stage, prove_host_run);
+  return mixed_dev(c, kProve, parts_of(p, nparts));
+}
+int gs_verify_mixed_dev(gs_ctx* c, int nparts, const gs_verify_part* p) {
+  RC(check_parts(c, nparts, p, "gs_verify_mixed: 0..8 parts"));
+  RangeGuard rg("gs.verify_mixed");
+  return mixed_dev(c, kVerify, parts_of(p, nparts));
+}
+int gs_prove_mixed(gs_ctx* c, int nparts, const gs_prove_part* p) {
+  RC(check_parts(c, nparts, p, "gs_prove_mixed: 0..8 parts"));
+  return mixed_host(c, kProve, parts_of(p, nparts), "gs.prove_mixed");
 }
 int gs_verify_mixed(gs_ctx* c, int nparts, const gs_verify_part* p) {
-  RC(check_ctx(c, true));
-  if (nparts < 0 || nparts > GS_MIXED_MAX || (nparts && !p)) return fail(c, GS_ERR_ARG, "gs_verify_mixed: 0..8 parts");
-  std::vector<VerifyArgs> a;
-  size_t tot = 0;
-  for (int i = 0; i < nparts; i++) {
-    RC(check_shape(c, p[i].equ_type, p[i].m, p[i].n));
-    if (p[i].N == 0) continue;
-    if (!p[i].A || !p[i].B || !p[i].Gamma || !p[i].target || !p[i].xcoms || !p[i].ycoms || !p[i].pi || !p[i].theta || !p[i].ok)
-      return fail(c, GS_ERR_ARG, "null pointer");
-    a.push_back(VerifyArgs{p[i].equ_type, p[i].N, p[i].m, p[i].n, p[i].A, p[i].B, p[i].Gamma, p[i].target, p[i].xcoms,
-                           p[i].ycoms, p[i].pi, p[i].theta, p[i].ok, p[i].shared_vars != 0});
-    tot += p[i].N;
-  }
-  RangeGuard rg("gs.verify_mixed");
-  return mixed_host(c, a, tot, verify_host_stage, verify_host_run);
-}
-
-// ---- Statement: E equations of one type over the SAME committed variables (statement.rs:24-28,109) -------------
-int gs_prove_statement_dev(gs_ctx* c, int ty, size_t E, int m, int n, const void* X, const void* Y, const void* A,
-                           const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
-                           void* ycoms, void* pi, void* theta) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (E == 0) return GS_OK;
-  if (!X || !Y || !A || !B || !G || !R || !S || !T || !pi || !theta) return fail(c, GS_ERR_ARG, "null pointer");
-  bool xg = x_is_group(ty), yg = y_is_group(ty);
-  // the commitments, once (commit.rs:78-100,125-156,178-200,225-256)
-  RC(need(c, BIT(PI_X) | BIT(PI_Y) | BIT(PI_R) | BIT(PI_S)));
-  if (xcoms) RC((xg ? gs_commit_g1_dev : gs_commit_fr_b1_dev)(c, (size_t)m, X, R, xcoms));
-  if (ycoms) RC((yg ? gs_commit_g2_dev : gs_commit_fr_b2_dev)(c, (size_t)n, Y, S, ycoms));
-  return DISPATCH(c, prove(c, ty, E, m, n, X, Y, A, B, G, R, S, T, nullptr, nullptr, pi, theta, true));
-}
-int gs_verify_statement_dev(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
-                            const void* target, const void* xcoms, const void* ycoms, const void* pi,
-                            const void* theta, uint8_t* ok) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (E == 0) return GS_OK;
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  return DISPATCH(c, verify(c, ty, E, m, n, A, B, G, target, xcoms, ycoms, pi, theta, ok, true));
-}
-int gs_prove_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* X, const void* Y, const void* A,
-                       const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
-                       void* ycoms, void* pi, void* theta) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (E == 0) return GS_OK;
-  if (!X || !Y || !A || !B || !G || !R || !S || !T || !pi || !theta) return fail(c, GS_ERR_ARG, "null pointer");
-  ProveArgs a{ty, E, m, n, X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta, true};
-  HostPipe hp(c);
-  RC(prove_host_stage(c, a, hp));
-  RC(prove_host_run(c, a, hp));
-  return hp.finish();
-}
-int gs_verify_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
-                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                        uint8_t* ok) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (E == 0) return GS_OK;
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  VerifyArgs a{ty, E, m, n, A, B, G, target, xcoms, ycoms, pi, theta, ok, true};
-  HostPipe hp(c);
-  RC(verify_host_stage(c, a, hp));
-  RC(verify_host_run(c, a, hp));
-  return hp.finish();
+  RC(check_parts(c, nparts, p, "gs_verify_mixed: 0..8 parts"));
+  return mixed_host(c, kVerify, parts_of(p, nparts), "gs.verify_mixed");
 }
 
 // ---- rerandomize: fresh commitments and proofs from old ones, without the witness -----------------------------
-struct RerandArgs {
-  int ty;
-  size_t N;
-  int m, n;
-  const void *A, *B, *G, *xc, *yc, *pi, *th, *R, *S, *T;
-  void *xco, *yco, *pio, *tho;
-  bool shared;  // a Statement: ONE copy of the commitments and of R', S' for all N equations
-};
-static int rerand_check(gs_ctx* c, const RerandArgs& a) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, a.ty, a.m, a.n));
-  if (a.N == 0) return GS_OK;
-  if (!a.A || !a.B || !a.G || !a.xc || !a.yc || !a.pi || !a.th || !a.R || !a.S || !a.T || !a.xco || !a.yco || !a.pio ||
-      !a.tho)
-    return fail(c, GS_ERR_ARG, "null pointer");
-  return GS_OK;
-}
-// byte sizes of the arrays, in the order A, B, G, xc, yc, pi, th, R, S, T, xco, yco, pio, tho
-static void rerand_sizes(gs_ctx* c, const RerandArgs& a, size_t sz[14]) {
-  size_t fq = sz_fq(c->curve), N = a.N, V = a.shared ? 1 : a.N;
-  bool xg = x_is_group(a.ty), yg = y_is_group(a.ty);
-  size_t kx = xg ? 2 : 1, ky = yg ? 2 : 1, m = (size_t)a.m, n = (size_t)a.n;
-  size_t sx = xg ? 2 * fq : SZ_FR, sy = yg ? 4 * fq : SZ_FR;
-  const size_t v[14] = {N * n * sx,          N * m * sy,          N * m * n * SZ_FR,  V * m * 4 * fq, V * n * 8 * fq,
-                        N * kx * 8 * fq,     N * ky * 4 * fq,     V * m * kx * SZ_FR, V * n * ky * SZ_FR,
-                        N * ky * kx * SZ_FR, V * m * 4 * fq,      V * n * 8 * fq,     N * kx * 8 * fq, N * ky * 4 * fq};
-  for (int i = 0; i < 14; i++) sz[i] = v[i];
-}
-static int rerand_dev(gs_ctx* c, const RerandArgs& a) {
-  RC(rerand_check(c, a));
-  if (a.N == 0) return GS_OK;
-  return DISPATCH(c, rerandomize(c, a.ty, a.N, a.m, a.n, a.A, a.B, a.G, a.xc, a.yc, a.pi, a.th, a.R, a.S, a.T, a.xco,
-                                 a.yco, a.pio, a.tho, a.shared));
-}
-static int rerand_host(gs_ctx* c, const RerandArgs& a) {
-  RC(rerand_check(c, a));
-  if (a.N == 0) return GS_OK;
-  size_t sz[14];
-  rerand_sizes(c, a, sz);
-  const void* p[14] = {a.A, a.B, a.G, a.xc, a.yc, a.pi, a.th, a.R, a.S, a.T, a.xco, a.yco, a.pio, a.tho};
-  // outputs do not alias inputs or each other (the device reads old commitments after it has written new ones)
-  for (int o = 10; o < 14; o++)
-    for (int i = 0; i < 14; i++) {
-      if (i == o) continue;
-      uintptr_t x = (uintptr_t)p[o], y = (uintptr_t)p[i];
-      if (x < y + sz[i] && y < x + sz[o]) return fail(c, GS_ERR_ARG, "rerandomize: an output overlaps another array");
-    }
-  HostPipe hp(c);
+static const ArrDesc kRerandArrs[] = {
+    {RI_A, lay::A, ARR_IN},       {RI_B, lay::B, ARR_IN},       {RI_G, lay::GAMMA, ARR_IN}, {RI_R, lay::R, ARR_IN},
+    {RI_S, lay::S, ARR_IN},       {RI_T, lay::T, ARR_IN},       {RI_XC, lay::XCOMS, ARR_IN}, {RI_YC, lay::YCOMS, ARR_IN},
+    {RI_PI, lay::PI, ARR_IN},     {RI_TH, lay::THETA, ARR_IN},  {RO_XC, lay::XCOMS, ARR_OUT}, {RO_YC, lay::YCOMS, ARR_OUT},
+    {RO_PI, lay::PI, ARR_OUT},    {RO_TH, lay::THETA, ARR_OUT}};
+static const int* rerand_order(int) {
   // staging order = the order rerandomize() asks for them: scalars, then the G2 side's arrays, then the G1 side's
-  static const int slot[14] = {RI_A, RI_B, RI_G, RI_XC, RI_YC, RI_PI, RI_TH, RI_R, RI_S, RI_T, RO_XC, RO_YC, RO_PI, RO_TH};
-  for (int i = 0; i < 10; i++) hp.in(slot[i], p[i], sz[i]);
-  for (int i = 10; i < 14; i++) hp.out(slot[i], (void*)p[i], sz[i]);
   static const int order[] = {RI_G, RI_R, RI_S, RI_T, RI_B, RI_A, RI_YC, RI_PI, RI_XC, RI_TH};
-  RC(hp.begin(order, 10));
-  RerandArgs d{a.ty, a.N, a.m, a.n, hp.dev(RI_A), hp.dev(RI_B), hp.dev(RI_G), hp.dev(RI_XC), hp.dev(RI_YC),
-               hp.dev(RI_PI), hp.dev(RI_TH), hp.dev(RI_R), hp.dev(RI_S), hp.dev(RI_T), hp.dev(RO_XC), hp.dev(RO_YC),
-               hp.dev(RO_PI), hp.dev(RO_TH), a.shared};
-  RC(rerand_dev(c, d));
-  return hp.finish();
+  return order;
+}
+static int rerand_run(gs_ctx* c, const BatchArgs& a) {
+  const void* const* p = a.p;
+  return DISPATCH(c, rerandomize(c, a.ty, a.N, a.m, a.n, p[RI_A], p[RI_B], p[RI_G], p[RI_XC], p[RI_YC], p[RI_PI],
+                                 p[RI_TH], p[RI_R], p[RI_S], p[RI_T], a.out(RO_XC), a.out(RO_YC), a.out(RO_PI),
+                                 a.out(RO_TH), a.shared));
+}
+static const Op kRerand = {kRerandArrs, sizeof kRerandArrs / sizeof *kRerandArrs, rerand_order, 10, rerand_run};
+// the arguments in the order of the public signatures -> slot order (the scalars R', S', T' come before the old
+// commitments and proofs there)
+static_assert(RI_R == 3 && RI_XC == 6 && RO_XC == 10 && RO_TH == 13, "rerand_args lists its pointers in slot order");
+static BatchArgs rerand_args(int ty, size_t N, int m, int n, bool shared, const void* A, const void* B, const void* G,
+                             const void* xc, const void* yc, const void* pi, const void* th, const void* R, const void* S,
+                             const void* T, void* xco, void* yco, void* pio, void* tho) {
+  return BatchArgs{ty, N, m, n, shared, {A, B, G, R, S, T, xc, yc, pi, th, xco, yco, pio, tho}};
+}
+static int rerand_host(gs_ctx* c, const BatchArgs& a) {
+  RC(batch_check(c, kRerand, a));
+  if (a.N == 0) return GS_OK;
+  // outputs do not alias inputs or each other (the device reads old commitments after it has written new ones)
+  const lay::Layout L = layout_of(c, a);
+  for (const ArrDesc& o : kRerandArrs) {
+    if (!(o.flags & ARR_OUT)) continue;
+    for (const ArrDesc& i : kRerandArrs) {
+      if (i.slot == o.slot) continue;
+      uintptr_t x = (uintptr_t)a.p[o.slot], y = (uintptr_t)a.p[i.slot];
+      if (x < y + L.bytes[i.arr] && y < x + L.bytes[o.arr])
+        return fail(c, GS_ERR_ARG, "rerandomize: an output overlaps another array");
+    }
+  }
+  return batch_host_checked(c, kRerand, a);
 }
 int gs_rerandomize_batch_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                              const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
                              const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
                              void* theta_out) {
-  return rerand_dev(c, RerandArgs{ty, N, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
-                                  theta_out, false});
+  return batch_dev(c, kRerand, rerand_args(ty, N, m, n, false, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out,
+                                           ycoms_out, pi_out, theta_out));
 }
 int gs_rerandomize_batch(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                          const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
                          const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out, void* theta_out) {
-  return rerand_host(c, RerandArgs{ty, N, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
-                                   theta_out, false});
+  return rerand_host(c, rerand_args(ty, N, m, n, false, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out,
+                                    pi_out, theta_out));
 }
 int gs_rerandomize_statement_dev(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
                                  const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
                                  const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
                                  void* theta_out) {
-  return rerand_dev(c, RerandArgs{ty, E, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
-                                  theta_out, true});
+  return batch_dev(c, kRerand, rerand_args(ty, E, m, n, true, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out,
+                                           ycoms_out, pi_out, theta_out));
 }
 int gs_rerandomize_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* A, const void* B, const void* G,
                              const void* xcoms, const void* ycoms, const void* pi, const void* theta, const void* R,
                              const void* S, const void* T, void* xcoms_out, void* ycoms_out, void* pi_out,
                              void* theta_out) {
-  return rerand_host(c, RerandArgs{ty, E, m, n, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out, pi_out,
-                                   theta_out, true});
+  return rerand_host(c, rerand_args(ty, E, m, n, true, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out,
+                                    pi_out, theta_out));
 }
 
 // ---- witness extraction with the binding key ---------------------------------------
@@ -3666,28 +3595,19 @@ int gs_verify_batch_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A
   RC(check_ctx(c, true));
   RC(check_shape(c, ty, m, n));
   if (N == 0) return fail(c, GS_ERR_ARG, "empty batch");
-  size_t fq = sz_fq(c->curve);
-  bool xg = x_is_group(ty), yg = y_is_group(ty);
-  int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
-  size_t sx = xg ? 2 * fq : SZ_FR, sy = yg ? 4 * fq : SZ_FR;
-  size_t st_ = ty == GS_PPE ? 12 * fq : ty == GS_MSMEG1 ? 2 * fq : ty == GS_MSMEG2 ? 4 * fq : SZ_FR;
   if (!rho) return fail(c, GS_ERR_ARG, "null pointer");
   for (size_t i = 0; i < 4 * N; i++)  // a zero exponent drops its cell equation from the combined check
     if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
   HostStage st(c);
-  void *dA, *dB, *dG, *dt, *dxc, *dyc, *dpi, *dth, *drho, *dacc;
-  std::vector<uint8_t> hacc(2 * 12 * fq);
-  RC(st.in(A, N * n * sx, &dA));
-  RC(st.in(B, N * m * sy, &dB));
-  RC(st.in(G, N * m * n * SZ_FR, &dG));
-  RC(st.in(target, N * st_, &dt));
-  RC(st.in(xcoms, N * m * 4 * fq, &dxc));
-  RC(st.in(ycoms, N * n * 8 * fq, &dyc));
-  RC(st.in(pi, N * kx * 8 * fq, &dpi));
-  RC(st.in(theta, N * ky * 4 * fq, &dth));
+  const lay::Layout L(sz_fq(c->curve), ty, N, m, n, false);
+  const void* const h[8] = {A, B, G, target, xcoms, ycoms, pi, theta};
+  static const lay::Array arr[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
+  void *d[8], *drho, *dacc;
+  std::vector<uint8_t> hacc(2 * 12 * sz_fq(c->curve));
+  for (int i = 0; i < 8; i++) RC(st.in(h[i], L.bytes[arr[i]], &d[i]));
   RC(st.in(rho, N * 4 * sizeof(uint64_t), &drho));
   RC(st.out(hacc.data(), hacc.size(), &dacc));
-  RC(gs_verify_batch_rlc_dev(c, ty, N, m, n, dA, dB, dG, dt, dxc, dyc, dpi, dth, (const uint64_t*)drho, dacc));
+  RC(gs_verify_batch_rlc_dev(c, ty, N, m, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], (const uint64_t*)drho, dacc));
   RC(st.back(hacc.data(), dacc, hacc.size()));
   if (acc) memcpy(acc, hacc.data(), hacc.size());
   if (ok_all) RC(gs_gt_finalize(c, 1, hacc.data(), ok_all));

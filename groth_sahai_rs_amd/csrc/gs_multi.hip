@@ -18,6 +18,7 @@
 // its block through its context's pinned pipeline) and `_dev` (per-shard DEVICE pointer arrays: shard i's block already
 // sits on devices[i], nothing crosses PCIe; asynchronous, gs_multi_sync joins).
 #include "../../include/gs_amd.h"
+#include "gs_layout.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -69,21 +70,17 @@ static Rccl load_rccl() {
   return r;
 }
 
-struct Shape {
-  size_t fq, fr, sx, sy, st;
-  int kx, ky;
+namespace lay = gs_layout;
+// Bytes of ONE equation's share of every array (gs_layout.h): shard i's block [lo, hi) of array a starts at
+// lo * stride[a].  False for an unknown equation type or curve.
+struct Stride {
+  size_t of[lay::NARRAYS];
 };
-static bool shape_of(int curve, int ty, Shape* s) {
+static bool stride_of(int curve, int ty, int m, int n, Stride* s) {
   size_t sz[6];
   if (ty < 0 || ty > 3 || gs_sizes(curve, sz) != GS_OK) return false;
-  bool xg = ty == GS_PPE || ty == GS_MSMEG1, yg = ty == GS_PPE || ty == GS_MSMEG2;
-  s->fq = sz[0];
-  s->fr = sz[1];
-  s->kx = xg ? 2 : 1;
-  s->ky = yg ? 2 : 1;
-  s->sx = xg ? sz[2] : sz[1];
-  s->sy = yg ? sz[3] : sz[1];
-  s->st = ty == GS_PPE ? sz[4] : ty == GS_MSMEG1 ? sz[2] : ty == GS_MSMEG2 ? sz[3] : sz[1];
+  const lay::Layout L = lay::Layout::stride(sz[0], ty, m, n);
+  std::copy(L.bytes, L.bytes + lay::NARRAYS, s->of);
   return true;
 }
 
@@ -185,6 +182,9 @@ static void block(size_t N, int ndev, int i, size_t* lo, size_t* hi) {
 }
 static inline const uint8_t* off(const void* p, size_t bytes) { return p ? (const uint8_t*)p + bytes : nullptr; }
 static inline uint8_t* offw(void* p, size_t bytes) { return p ? (uint8_t*)p + bytes : nullptr; }
+// the start of a block of equations beginning at `lo` in array `ARR` of the whole batch
+#define AT(p, ARR) off(p, lo * s.of[lay::ARR])
+#define ATW(p, ARR) offw(p, lo * s.of[lay::ARR])
 
 // run fn(i) for every shard on its worker; first non-zero status wins
 template <class F> static int on_all(gs_multi* m, F fn) {
@@ -514,20 +514,16 @@ int gs_multi_prove_batch(gs_multi* m, int ty, size_t N, int mm, int n, const voi
                          const void* B, const void* G, const void* R, const void* S, const void* T, void* xcoms,
                          void* ycoms, void* pi, void* theta) {
   if (!m) return GS_ERR_ARG;
-  Shape s;
-  if (!shape_of(m->curve, ty, &s)) return mfail(m, GS_ERR_ARG, "bad equation type");
+  Stride s;
+  if (!stride_of(m->curve, ty, mm, n, &s)) return mfail(m, GS_ERR_ARG, "bad equation type");
   if (mm < 1 || n < 1) return mfail(m, GS_ERR_SHAPE, "m and n must be >= 1 (reference asserts, prove.rs:106-113)");
   int nd = (int)m->ctx.size();
   return on_all(m, [&](int i) {
     size_t lo, hi;
     block(N, nd, i, &lo, &hi);
     if (hi == lo) return (int)GS_OK;
-    size_t um = (size_t)mm, un = (size_t)n;
-    return gs_prove_batch(m->ctx[i], ty, hi - lo, mm, n, off(X, lo * um * s.sx), off(Y, lo * un * s.sy),
-                          off(A, lo * un * s.sx), off(B, lo * um * s.sy), off(G, lo * um * un * s.fr),
-                          off(R, lo * um * s.kx * s.fr), off(S, lo * un * s.ky * s.fr), off(T, lo * s.ky * s.kx * s.fr),
-                          offw(xcoms, lo * um * 4 * s.fq), offw(ycoms, lo * un * 8 * s.fq), offw(pi, lo * s.kx * 8 * s.fq),
-                          offw(theta, lo * s.ky * 4 * s.fq));
+    return gs_prove_batch(m->ctx[i], ty, hi - lo, mm, n, AT(X, X), AT(Y, Y), AT(A, A), AT(B, B), AT(G, GAMMA), AT(R, R),
+                          AT(S, S), AT(T, T), ATW(xcoms, XCOMS), ATW(ycoms, YCOMS), ATW(pi, PI), ATW(theta, THETA));
   });
 }
 
@@ -535,24 +531,21 @@ int gs_multi_verify_batch(gs_multi* m, int ty, size_t N, int mm, int n, const vo
                           const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
                           uint8_t* ok) {
   if (!m) return GS_ERR_ARG;
-  Shape s;
-  if (!shape_of(m->curve, ty, &s)) return mfail(m, GS_ERR_ARG, "bad equation type");
+  Stride s;
+  if (!stride_of(m->curve, ty, mm, n, &s)) return mfail(m, GS_ERR_ARG, "bad equation type");
   if (mm < 1 || n < 1) return mfail(m, GS_ERR_SHAPE, "m and n must be >= 1");
   int nd = (int)m->ctx.size();
   return on_all(m, [&](int i) {
     size_t lo, hi;
     block(N, nd, i, &lo, &hi);
     if (hi == lo) return (int)GS_OK;
-    size_t um = (size_t)mm, un = (size_t)n;
-    return gs_verify_batch(m->ctx[i], ty, hi - lo, mm, n, off(A, lo * un * s.sx), off(B, lo * um * s.sy),
-                           off(G, lo * um * un * s.fr), off(target, lo * s.st), off(xcoms, lo * um * 4 * s.fq),
-                           off(ycoms, lo * un * 8 * s.fq), off(pi, lo * s.kx * 8 * s.fq), off(theta, lo * s.ky * 4 * s.fq),
-                           ok ? ok + lo : nullptr);
+    return gs_verify_batch(m->ctx[i], ty, hi - lo, mm, n, AT(A, A), AT(B, B), AT(G, GAMMA), AT(target, TARGET),
+                           AT(xcoms, XCOMS), AT(ycoms, YCOMS), AT(pi, PI), AT(theta, THETA), ATW(ok, OK));
   });
 }
 
-static int rlc_prologue(gs_multi* m, int ty, size_t N, int mm, int n, Shape* s) {
-  if (!shape_of(m->curve, ty, s)) return mfail(m, GS_ERR_ARG, "bad equation type");
+static int rlc_prologue(gs_multi* m, int ty, size_t N, int mm, int n, Stride* s) {
+  if (!stride_of(m->curve, ty, mm, n, s)) return mfail(m, GS_ERR_ARG, "bad equation type");
   if (mm < 1 || n < 1) return mfail(m, GS_ERR_SHAPE, "m and n must be >= 1");
   if (N == 0) return mfail(m, GS_ERR_ARG, "empty batch");
   int rc = exchange_setup(m);
@@ -579,7 +572,7 @@ int gs_multi_verify_batch_rlc(gs_multi* m, int ty, size_t N, int mm, int n, cons
                               const void* theta, const uint64_t* rho, void* acc_pairs, uint8_t* ok_all) {
   if (!m || !ok_all) return GS_ERR_ARG;
   if (!rho) return mfail(m, GS_ERR_ARG, "rho is NULL (see the rho contract in gs_amd.h)");
-  Shape s;
+  Stride s;
   int rc = rlc_prologue(m, ty, N, mm, n, &s);
   if (rc != GS_OK) return rc;
   int nd = (int)m->ctx.size();
@@ -588,13 +581,11 @@ int gs_multi_verify_batch_rlc(gs_multi* m, int ty, size_t N, int mm, int n, cons
     size_t lo, hi;
     block(N, nd, i, &lo, &hi);
     if (hi == lo) return empty_pair(m, i);
-    size_t um = (size_t)mm, un = (size_t)n;
     // (host inputs: the shard's pair comes back with them and goes up into its exchange buffer, 1152 bytes)
     std::vector<uint8_t> acc(pair);
-    int r = gs_verify_batch_rlc(m->ctx[i], ty, hi - lo, mm, n, off(A, lo * un * s.sx), off(B, lo * um * s.sy),
-                                off(G, lo * um * un * s.fr), off(target, lo * s.st), off(xcoms, lo * um * 4 * s.fq),
-                                off(ycoms, lo * un * 8 * s.fq), off(pi, lo * s.kx * 8 * s.fq),
-                                off(theta, lo * s.ky * 4 * s.fq), rho + 4 * lo, acc.data(), nullptr);
+    int r = gs_verify_batch_rlc(m->ctx[i], ty, hi - lo, mm, n, AT(A, A), AT(B, B), AT(G, GAMMA), AT(target, TARGET),
+                                AT(xcoms, XCOMS), AT(ycoms, YCOMS), AT(pi, PI), AT(theta, THETA), rho + 4 * lo, acc.data(),
+                                nullptr);
     if (r != GS_OK) return r;
     return hipMemcpy(m->sendb[i], acc.data(), pair, hipMemcpyHostToDevice) == hipSuccess ? (int)GS_OK : (int)GS_ERR_DEVICE;
   });
@@ -603,6 +594,8 @@ int gs_multi_verify_batch_rlc(gs_multi* m, int ty, size_t N, int mm, int n, cons
 }
 
 // ---- device-resident shards: per-shard pointer arrays, nothing crosses PCIe --------------------------------------
+#undef AT
+#undef ATW
 #define PP(a) ((a) ? (a)[i] : nullptr)
 int gs_multi_prove_batch_dev(gs_multi* m, int ty, size_t N, int mm, int n, const void* const* X, const void* const* Y,
                              const void* const* A, const void* const* B, const void* const* G, const void* const* R,
@@ -643,7 +636,7 @@ int gs_multi_verify_batch_rlc_dev(gs_multi* m, int ty, size_t N, int mm, int n, 
                                   uint8_t* ok_all) {
   if (!m || !ok_all) return GS_ERR_ARG;
   if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho) return mfail(m, GS_ERR_ARG, "null pointer array");
-  Shape s;
+  Stride s;
   int rc = rlc_prologue(m, ty, N, mm, n, &s);
   if (rc != GS_OK) return rc;
   int nd = (int)m->ctx.size();
