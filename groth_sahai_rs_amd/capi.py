@@ -37,7 +37,11 @@ SYMBOLS = [
     "gs_prove_mixed_dev", "gs_prove_mixed", "gs_verify_mixed_dev", "gs_verify_mixed",
     "gs_rerandomize_batch_dev", "gs_rerandomize_batch", "gs_rerandomize_statement_dev", "gs_rerandomize_statement",
     "gs_set_extraction_key", "gs_extract_g1_dev", "gs_extract_g2_dev", "gs_extract_g1", "gs_extract_g2",
+    "gs_dlog_prepare", "gs_dlog_g1_dev", "gs_dlog_g2_dev", "gs_dlog_g1", "gs_dlog_g2",
+    "gs_extract_scalar_b1_dev", "gs_extract_scalar_b2_dev", "gs_extract_scalar_b1", "gs_extract_scalar_b2",
 ]
+# (size_t count, const void* in, unsigned bits, void* out_fr, void* found_u8) behind the context
+_DLOG_ARGTYPES = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
 GS_MIXED_MAX = 8
 GS_MULTI_SHARED_DEVICES = 1
 
@@ -87,6 +91,10 @@ def load_library():
         _LIB = ctypes.CDLL(p)
         _LIB.gs_last_error.restype = ctypes.c_char_p
         _LIB.gs_version.restype = ctypes.c_char_p
+        _LIB.gs_dlog_prepare.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint]
+        for n in SYMBOLS:
+            if n.startswith(("gs_dlog_g", "gs_extract_scalar_")):
+                getattr(_LIB, n).argtypes = _DLOG_ARGTYPES
     return _LIB
 
 
@@ -364,6 +372,49 @@ class Engine:
         self._chk(getattr(self.lib, fn)(self.ctx, ctypes.c_size_t(n), _p(coms), _p(out)))
         return out.reshape(n, gsz)
 
+    def dlog_prepare(self, group, base, log2_table):
+        """Build the baby-step table j * base, j = 1 .. 2^log2_table, for group 1 | 2 (gs_dlog_prepare): 2^(log2_table + 1)
+        slots of 8 bytes on the device.  A second call for the group replaces the table."""
+        if group not in (1, 2):
+            raise GsError(3, "gs_dlog_prepare: group must be 1 or 2")
+        base = _u8(base)
+        _need("gs_dlog_prepare", [("base", base, self.G1 if group == 1 else self.G2)])
+        tabs = self.__dict__.setdefault("_dlog_tables", {})
+        tabs.pop(group, None)  # a refused call may already have dropped the old table
+        self._chk(self.lib.gs_dlog_prepare(self.ctx, group, _p(base), int(log2_table)))
+        tabs[group] = (base.tobytes(), int(log2_table))
+
+    def dlog_table(self, group):
+        """(base bytes, log2_table) of the table the last successful dlog_prepare built for the group, or None."""
+        return self.__dict__.get("_dlog_tables", {}).get(group)
+
+    def _check_dlog(self, fn, group, pts, out=None, found=None, coms=False):
+        """Byte lengths of a bounded discrete logarithm: whole points (coms: whole commitments) in, one Fr and one
+        found byte per element out.  Returns the count."""
+        if group not in (1, 2):
+            raise GsError(3, "%s: group must be 1 or 2" % fn)
+        isz = (self.G1 if group == 1 else self.G2) * (2 if coms else 1)
+        n = _nbytes(pts) // isz
+        _need(fn, [("coms" if coms else "pts", pts, n * isz), ("out", out, n * self.FR), ("found", found, n)])
+        return n
+
+    def _dlog_host(self, fn, group, arr, bits, coms):
+        arr = _u8(arr)
+        n = self._check_dlog(fn, group, arr, coms=coms)
+        out, found = self._out(n * self.FR), self._out(n)
+        self._chk(getattr(self.lib, fn)(self.ctx, n, _p(arr), int(bits), _p(out), _p(found)))
+        return out.reshape(n, self.FR), found
+
+    def dlog(self, group, pts, bits):
+        """(xs, found): found[i] = 1 and xs[i] = x (an Fr as commit("fr_b1") takes it) when 0 <= x < 2^bits with
+        x * base == pts[i] exists, else 0 and all-zero bytes (gs_dlog_g1 / gs_dlog_g2; base: dlog_prepare)."""
+        return self._dlog_host("gs_dlog_g1" if group == 1 else "gs_dlog_g2", group, pts, bits, False)
+
+    def extract_scalar(self, group, coms, bits):
+        """(xs, found) of scalar commitments opened with the installed binding key: extract, then dlog on the images
+        (gs_extract_scalar_b1 / _b2).  The table must have been prepared with the CRS generator of the group."""
+        return self._dlog_host("gs_extract_scalar_b1" if group == 1 else "gs_extract_scalar_b2", group, coms, bits, True)
+
     def verify_batch(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, ok=None):
         if ok is None:
             ok = np.zeros(N, dtype=np.uint8)
@@ -514,6 +565,16 @@ class Engine:
         fn = "gs_extract_g1_dev" if group == 1 else "gs_extract_g2_dev"
         n = self._check_extract(fn, group, coms, out)
         self._chk(getattr(self.lib, fn)(self.ctx, ctypes.c_size_t(n), _p(coms), _p(out)))
+
+    def dlog_dev(self, group, pts, bits, out, found):
+        fn = "gs_dlog_g1_dev" if group == 1 else "gs_dlog_g2_dev"
+        n = self._check_dlog(fn, group, pts, out, found)
+        self._chk(getattr(self.lib, fn)(self.ctx, n, _p(pts), int(bits), _p(out), _p(found)))
+
+    def extract_scalar_dev(self, group, coms, bits, out, found):
+        fn = "gs_extract_scalar_b1_dev" if group == 1 else "gs_extract_scalar_b2_dev"
+        n = self._check_dlog(fn, group, coms, out, found, coms=True)
+        self._chk(getattr(self.lib, fn)(self.ctx, n, _p(coms), int(bits), _p(out), _p(found)))
 
     def multi_pairing_batch_dev(self, n, k, P, Q, out):
         self._chk(self.lib.gs_multi_pairing_batch_dev(self.ctx, ctypes.c_size_t(n), k, _p(P), _p(Q), _p(out)))

@@ -142,6 +142,15 @@ struct gs_ctx {
   // without the endomorphism, G2 likewise.  They are the secret: zeroed when the key goes (clear_extraction_key).
   DevBuf xkey;
   bool have_xkey = false;
+  // baby-step tables of gs_dlog_prepare, one per group ([0] G1, [1] G2): public data, not tied to the CRS
+  struct DlogTab {
+    DevBuf slots;  // 2^(log2_table + 1) x u64
+    DevBuf aux;    // the base point (boundary bytes, padded to 256) followed by the K giant steps (internal form)
+    unsigned log2_table = 0;
+    bool ready = false;
+  } dlog[2];
+  int dlog_steps = 0;    // giant steps per launch; 0 = DLOG_STEPS_DEFAULT
+  int dlog_fp_bits = 0;  // fingerprint bits compared on a lookup; 0 = all of them
 };
 
 // Every live context of the process (gs_ctx_create .. gs_ctx_destroy): page-locked caller ranges are process-wide
@@ -2722,6 +2731,9 @@ void gs_ctx_destroy(gs_ctx* c) {
   drain_ctx(c);
   clear_extraction_key(c);
   if (c->xkey.p) hipFree(c->xkey.p);
+  for (auto& t : c->dlog)
+    for (DevBuf* b : {&t.slots, &t.aux})
+      if (b->p) hipFree(b->p);
   for (void* p : c->deferred_free) hipFree(p);
   if (c->stamp) hipFree(c->stamp);
   for (auto& kv : c->scratch)
@@ -2795,6 +2807,12 @@ int gs_set_option(gs_ctx* c, const char* key, int value) {
   } else if (k == "coop_fe") {
     if (value < 0 || value > 2) return fail(c, GS_ERR_ARG, "coop_fe: 0 never, 1 planned, 2 always");
     c->coop_fe = value;
+  } else if (k == "dlog_steps") {
+    if (value < 0) return fail(c, GS_ERR_ARG, "dlog_steps: 0 (default) or the giant steps per launch");
+    c->dlog_steps = value;
+  } else if (k == "dlog_fp_bits") {
+    if (value < 0 || value > DLOG_FP_BITS) return fail(c, GS_ERR_ARG, "dlog_fp_bits: 0 (default) or 1 .. 35 fingerprint bits");
+    c->dlog_fp_bits = value;
   } else if (k == "line_tables") {
     c->line_tables = value != 0;
   } else if (k == "overlap") {
@@ -3446,6 +3464,173 @@ int gs_extract_g2_dev(gs_ctx* c, size_t n, const void* coms, void* out) {
   }
 EXTRACT_HOST(gs_extract_g1, gs_extract_g1_dev, 2)
 EXTRACT_HOST(gs_extract_g2, gs_extract_g2_dev, 4)
+
+// ---- bounded discrete logarithms: baby-step giant-step (csrc/gs_kernels.cuh: k_dlog_table, k_dlog) ------------------
+}  // extern "C"
+static const size_t DLOG_AUX_STEPS = 256;  // offset of the giant steps behind the base point in DlogTab::aux
+template <class C, class F> static int dlog_prepare_impl(gs_ctx* c, int gi, const void* base_host, unsigned log2_table) {
+  gs_ctx::DlogTab& t = c->dlog[gi];
+  const size_t pt = AFFB(C, F);
+  static_assert(AFFB(C, F) <= DLOG_AUX_STEPS, "base point in front of the giant steps");
+  constexpr int K = DlogShape<F>::K;
+  const size_t slot_bytes = sizeof(uint64_t) << (log2_table + 1);
+  // replace: nothing enqueued may still read the old table; the old one is freed before the new one is asked for
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  t.ready = false;
+  if (t.slots.p && t.slots.cap != slot_bytes) {
+    hipFree(t.slots.p);
+    t.slots = DevBuf();
+  }
+  if (!t.slots.p) {
+    hipError_t e = hipMalloc(&t.slots.p, slot_bytes);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      t.slots = DevBuf();
+      return fail(c, GS_ERR_ALLOC, "gs_dlog_prepare: the table does not fit (2^(log2_table+1) slots of 8 bytes)", e);
+    }
+    t.slots.cap = slot_bytes;
+  }
+  RC(ensure(c, t.aux, DLOG_AUX_STEPS + K * sizeof(Aff<F>)));
+  uint8_t* aux = (uint8_t*)t.aux.p;
+  HIPCHK(c, hipMemcpyAsync(aux, base_host, pt, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(t.slots.p, 0, slot_bytes, c->stream));
+  const size_t B = (size_t)1 << log2_table;
+  const int run = B < (size_t)DLOG_RUN ? (int)B : DLOG_RUN;
+  const char* names[2][2] = {{"k_dlog_table.g1", "k_dlog_steps.g1"}, {"k_dlog_table.g2", "k_dlog_steps.g2"}};
+  c->work_hint = B;
+  RC(launch_seg<k_dlog_table<C, F>>(c, names[gi][0], B / run, 64, B / run, (const uint8_t*)aux, run, log2_table + 1,
+                                    (unsigned long long*)t.slots.p));
+  RC(launch(c, names[gi][1], k_dlog_steps<C, F>, K, 64, (const uint8_t*)aux, (uint64_t)(2 * B), K,
+            (Aff<F>*)(aux + DLOG_AUX_STEPS)));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // base_host is the caller's again
+  t.log2_table = log2_table;
+  t.ready = true;
+  return GS_OK;
+}
+// pts, out, found: device pointers; checked by the caller
+template <class C, class F>
+static int dlog_run_impl(gs_ctx* c, int gi, size_t n, const void* pts, unsigned bits, void* out, void* found) {
+  const gs_ctx::DlogTab& t = c->dlog[gi];
+  const uint8_t* aux = (const uint8_t*)t.aux.p;
+  const unsigned T = t.log2_table;
+  const uint64_t centres = bits > T + 1 ? (uint64_t)1 << (bits - T - 1) : 1;  // stride 2^(T+1) over [0, 2^bits)
+  const uint64_t per = c->dlog_steps ? (uint64_t)c->dlog_steps : (uint64_t)DLOG_STEPS_DEFAULT;
+  const unsigned fpb = c->dlog_fp_bits ? (unsigned)c->dlog_fp_bits : (unsigned)DLOG_FP_BITS;
+  const char* name = gi == 0 ? "k_dlog.g1" : "k_dlog.g2";
+  for (uint64_t t0 = 0; t0 < centres; t0 += per) {
+    const uint32_t ns = (uint32_t)std::min(per, centres - t0);
+    c->work_hint = (uint64_t)n * ns;
+    RC(launch_seg<k_dlog<C, F>>(c, name, n, 64, n, (const uint8_t*)pts, aux, (const Aff<F>*)(aux + DLOG_AUX_STEPS),
+                                (const unsigned long long*)t.slots.p, T + 1, T, bits, fpb, t0, ns, t0 == 0 ? 1 : 0,
+                                (Fr<C>*)out, (uint8_t*)found));
+  }
+  return GS_OK;
+}
+static bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb) {
+  const uint8_t *x = (const uint8_t*)a, *y = (const uint8_t*)b;
+  return x < y + nb && y < x + na;
+}
+// everything gs_dlog_* refuses, in one place; in_bytes = bytes of the input array per element
+static int dlog_check(gs_ctx* c, const char* fn, int gi, size_t n, const void* in, size_t in_bytes, unsigned bits,
+                      void* out, void* found) {
+  if (c->rec) return fail(c, GS_ERR_ARG, (std::string(fn) + " inside a mixed call").c_str());
+  const gs_ctx::DlogTab& t = c->dlog[gi];
+  if (!t.ready) return fail(c, GS_ERR_ARG, (std::string(fn) + ": gs_dlog_prepare has not been called for this group").c_str());
+  if (bits < 1 || bits > 48) return fail(c, GS_ERR_ARG, (std::string(fn) + ": bits must be 1 .. 48").c_str());
+  if (bits > t.log2_table + 25) {
+    char msg[200];
+    snprintf(msg, sizeof msg, "%s: bits = %u needs more than 2^24 giant steps with log2_table = %u; prepare log2_table >= %u",
+             fn, bits, t.log2_table, bits - 25);
+    return fail(c, GS_ERR_ARG, msg);
+  }
+  if (n == 0) return GS_OK;
+  if (!in || !out || !found) return fail(c, GS_ERR_ARG, "null pointer");
+  if (ranges_overlap(in, n * in_bytes, out, n * SZ_FR) || ranges_overlap(in, n * in_bytes, found, n) ||
+      ranges_overlap(out, n * SZ_FR, found, n))
+    return fail(c, GS_ERR_ARG, (std::string(fn) + ": outputs overlap the input or each other").c_str());
+  return GS_OK;
+}
+static int dlog_dev(gs_ctx* c, const char* fn, int gi, size_t n, const void* pts, unsigned bits, void* out, void* found) {
+  RC(check_ctx(c, false));
+  RC(dlog_check(c, fn, gi, n, pts, (gi ? 4 : 2) * sz_fq(c->curve), bits, out, found));
+  if (n == 0) return GS_OK;
+  if (gi == 0)
+    return WIRE_DISPATCH((dlog_run_impl<Bls12_381, Fq<Bls12_381>>(c, 0, n, pts, bits, out, found)),
+                         (dlog_run_impl<Bn254, Fq<Bn254>>(c, 0, n, pts, bits, out, found)));
+  return WIRE_DISPATCH((dlog_run_impl<Bls12_381, Fp2<Bls12_381>>(c, 1, n, pts, bits, out, found)),
+                       (dlog_run_impl<Bn254, Fp2<Bn254>>(c, 1, n, pts, bits, out, found)));
+}
+// k_extract into context scratch, then the walk over the images
+static int extract_scalar_dev(gs_ctx* c, const char* fn, int gi, size_t n, const void* coms, unsigned bits, void* out,
+                              void* found) {
+  RC(check_ctx(c, true));
+  if (!c->have_xkey) return fail(c, GS_ERR_ARG, "gs_set_extraction_key has not been called");
+  const size_t pt = (gi ? 4 : 2) * sz_fq(c->curve);
+  RC(dlog_check(c, fn, gi, n, coms, 2 * pt, bits, out, found));
+  if (n == 0) return GS_OK;
+  void* img;
+  RC(scratch(c, gi ? "xs.img2" : "xs.img1", n * pt, &img));
+  RC(gi ? gs_extract_g2_dev(c, n, coms, img) : gs_extract_g1_dev(c, n, coms, img));
+  return dlog_dev(c, fn, gi, n, img, bits, out, found);
+}
+// the host forms: stage in, run the _dev form, copy both outputs back
+static int dlog_host(gs_ctx* c, const char* fn, int gi, bool coms, size_t n, const void* in, unsigned bits, void* out,
+                     void* found) {
+  RC(check_ctx(c, coms));
+  if (coms && !c->have_xkey) return fail(c, GS_ERR_ARG, "gs_set_extraction_key has not been called");
+  const size_t in_bytes = (coms ? 2 : 1) * (gi ? 4 : 2) * sz_fq(c->curve);
+  RC(dlog_check(c, fn, gi, n, in, in_bytes, bits, out, found));
+  if (n == 0) return GS_OK;
+  HostStage st(c);
+  void *din, *dout, *dfound;
+  RC(st.in(in, n * in_bytes, &din));
+  RC(st.out(out, n * SZ_FR, &dout));
+  RC(st.out(found, n, &dfound));
+  RC(coms ? extract_scalar_dev(c, fn, gi, n, din, bits, dout, dfound) : dlog_dev(c, fn, gi, n, din, bits, dout, dfound));
+  RC(st.back(out, dout, n * SZ_FR));
+  return st.back(found, dfound, n);
+}
+extern "C" {
+int gs_dlog_prepare(gs_ctx* c, int group, const void* base_host, unsigned log2_table) {
+  RC(check_ctx(c, false));
+  if (c->rec) return fail(c, GS_ERR_ARG, "gs_dlog_prepare inside a mixed call");
+  if (group != 1 && group != 2) return fail(c, GS_ERR_ARG, "gs_dlog_prepare: group must be 1 or 2");
+  if (log2_table < 2 || log2_table > 28) return fail(c, GS_ERR_ARG, "gs_dlog_prepare: log2_table must be 2 .. 28");
+  if (!base_host) return fail(c, GS_ERR_ARG, "null pointer");
+  const size_t pt = (group == 2 ? 4 : 2) * sz_fq(c->curve);
+  bool zero = true;
+  for (size_t i = 0; i < pt; i++) zero = zero && ((const uint8_t*)base_host)[i] == 0;
+  if (zero) return fail(c, GS_ERR_ARG, "gs_dlog_prepare: the base is the identity");
+  if (group == 1)
+    return WIRE_DISPATCH((dlog_prepare_impl<Bls12_381, Fq<Bls12_381>>(c, 0, base_host, log2_table)),
+                         (dlog_prepare_impl<Bn254, Fq<Bn254>>(c, 0, base_host, log2_table)));
+  return WIRE_DISPATCH((dlog_prepare_impl<Bls12_381, Fp2<Bls12_381>>(c, 1, base_host, log2_table)),
+                       (dlog_prepare_impl<Bn254, Fp2<Bn254>>(c, 1, base_host, log2_table)));
+}
+int gs_dlog_g1_dev(gs_ctx* c, size_t n, const void* pts, unsigned bits, void* out, void* found) {
+  return dlog_dev(c, "gs_dlog_g1_dev", 0, n, pts, bits, out, found);
+}
+int gs_dlog_g2_dev(gs_ctx* c, size_t n, const void* pts, unsigned bits, void* out, void* found) {
+  return dlog_dev(c, "gs_dlog_g2_dev", 1, n, pts, bits, out, found);
+}
+int gs_dlog_g1(gs_ctx* c, size_t n, const void* pts, unsigned bits, void* out, void* found) {
+  return dlog_host(c, "gs_dlog_g1", 0, false, n, pts, bits, out, found);
+}
+int gs_dlog_g2(gs_ctx* c, size_t n, const void* pts, unsigned bits, void* out, void* found) {
+  return dlog_host(c, "gs_dlog_g2", 1, false, n, pts, bits, out, found);
+}
+int gs_extract_scalar_b1_dev(gs_ctx* c, size_t n, const void* coms, unsigned bits, void* out, void* found) {
+  return extract_scalar_dev(c, "gs_extract_scalar_b1_dev", 0, n, coms, bits, out, found);
+}
+int gs_extract_scalar_b2_dev(gs_ctx* c, size_t n, const void* coms, unsigned bits, void* out, void* found) {
+  return extract_scalar_dev(c, "gs_extract_scalar_b2_dev", 1, n, coms, bits, out, found);
+}
+int gs_extract_scalar_b1(gs_ctx* c, size_t n, const void* coms, unsigned bits, void* out, void* found) {
+  return dlog_host(c, "gs_extract_scalar_b1", 0, true, n, coms, bits, out, found);
+}
+int gs_extract_scalar_b2(gs_ctx* c, size_t n, const void* coms, unsigned bits, void* out, void* found) {
+  return dlog_host(c, "gs_extract_scalar_b2", 1, true, n, coms, bits, out, found);
+}
 
 // ---- helpers / hooks -----------------------------------------------------------
 int gs_g1_mul_batch_dev(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {

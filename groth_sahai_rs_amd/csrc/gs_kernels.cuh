@@ -263,6 +263,259 @@ __global__ void __launch_bounds__(64, GS_WPE) k_extract_key(const Fr<C>* key, co
   }
 }
 
+// ---- bounded discrete logarithms (gs_dlog_*, gs_extract_scalar_*) ------------------------------------------------------
+// Baby-step giant-step for x in [0, 2^bits) with x G = P.  B = 2^log2_table baby steps j G,
+// j = 1..B, are kept by the x coordinate alone (one entry serves +j and -j) in an open-addressing table of 2 B slots of
+// 64 bits, slot = fingerprint << 29 | j, 0 = empty.  The giant steps have stride S = 2 B and centres c_t = B + t S:
+// x = c_t + d, d in [-B, B), and the lane looks for the x coordinate of Q_t = P - c_t G = d G in the table.
+constexpr int DLOG_JBITS = 29;                 // j <= 2^28
+constexpr int DLOG_FP_BITS = 64 - DLOG_JBITS;  // fingerprint bits of a slot (the default of "dlog_fp_bits")
+constexpr int DLOG_RUN = 8;                    // consecutive baby steps per lane of k_dlog_table
+// LDS of a k_dlog block (one wave): a quarter of the CU's 160 KB, so that each of its four SIMDs holds a wave
+constexpr int DLOG_LDS_BYTES = 40 * 1024;
+constexpr int DLOG_KMAX = 16;
+// giant steps per launch unless "dlog_steps" says otherwise.  An ESTIMATE, not a measured optimum: ~6 Fq
+// multiplications per G1 step at ~2 10^6 multiplications per second and lane make this ~0.1 s (G2 ~0.3 s).
+constexpr uint32_t DLOG_STEPS_DEFAULT = 1u << 15;
+template <class F> struct DlogShape {
+  static constexpr int NW = (int)(sizeof(F) / sizeof(limb_t));
+  static constexpr int KFIT = DLOG_LDS_BYTES / (64 * (int)sizeof(F));
+  // giant steps under one shared inversion: what fits the block's LDS share (BLS12-381: 11 in G1, 5 in G2; BN254: 16, 8)
+  static constexpr int K = KFIT > DLOG_KMAX ? DLOG_KMAX : KFIT;
+  static_assert(K >= 2, "giant steps per inversion");
+};
+
+// The key of a coordinate: its CANONICAL value (two lazy representations of one x must hash alike), all words mixed.
+template <class C, class F> __device__ __forceinline__ uint64_t dlog_hash(const F& x) {
+  uint32_t w[NCoord<F>::V][C::N];
+  coord_words<C>(w, x);
+  uint64_t h = 0x243F6A8885A308D3ull;
+  for (int a = 0; a < NCoord<F>::V; a++)
+    for (int i = 0; i < C::N; i++) {
+      h = (h ^ w[a][i]) * 0x9E3779B97F4A7C15ull;
+      h ^= h >> 29;
+    }
+  h *= 0xD6E8FEB86659FD93ull;
+  return h ^ (h >> 32);
+}
+// r = k G for a short scalar: plain double-and-add from the top bit, full edge cases (any curve point)
+template <class F> GS_HD_NOINLINE void jac_smul_u64(Jac<F>& rout, const Aff<F>& g, uint64_t k) {
+  Jac<F> r;
+  jac_set_inf(r);
+  int top = -1;
+  for (int i = 0; i < 64; i++)
+    if ((k >> i) & 1) top = i;
+#pragma unroll 1
+  for (int i = top; i >= 0; i--) {
+    jac_dbl(r, r);
+    if ((k >> i) & 1) jac_madd_edge(r, r, g);
+  }
+  rout = r;
+}
+// x G == P on full coordinates (P is not the identity)
+template <class C, class F> GS_HD_NOINLINE bool dlog_confirm(const Aff<F>& G, const Aff<F>& P, uint64_t x) {
+  Jac<F> j;
+  jac_smul_u64(j, G, x);
+  if (is_zero_limbs(j.z)) return false;
+  Aff<F> r;
+  jac_to_aff(r, j);
+  return eq(r.x, P.x) && eq(r.y, P.y);  // exact comparisons mod p
+}
+
+// Baby steps: lane g owns j = g run + 1 .. g run + run.  Its first point is one short scalar multiplication, the rest
+// of the run additions of G on the Jacobian point; the run is normalised with ONE inversion (as k_red shares one).
+// Entries are inserted by 64-bit compare-and-swap with linear probing: the order of insertion varies from run to run,
+// the SET of entries a probe sequence meets before its first empty slot does not.
+template <class C, class F>
+struct k_dlog_table {
+  static __device__ __forceinline__ void run(size_t g, size_t total, const uint8_t* base, int run, unsigned log2_slots,
+                                            unsigned long long* slots) {
+  if (g >= total) return;
+  Aff<F> G;
+  aff_load<C>(G, base);
+  Jac<F> cur;
+  jac_smul_u64(cur, G, (uint64_t)g * run + 1);
+  F xs[DLOG_RUN], zs[DLOG_RUN], pre[DLOG_RUN];
+  F acc = one_of<F>();
+  uint32_t inf = 0;  // j G = O: only a base of small order gets here; no entry
+#pragma unroll 1
+  for (int i = 0; i < run; i++) {
+    if (i) jac_madd_edge(cur, cur, G);
+    xs[i] = cur.x;
+    zs[i] = cur.z;
+    pre[i] = acc;
+    if (gz_is_zero<C>(cur.z))
+      inf |= 1u << i;
+    else
+      acc = mul(acc, cur.z);
+  }
+  F suf = inv(acc);
+  const uint64_t mask = ((uint64_t)1 << log2_slots) - 1;
+#pragma unroll 1
+  for (int i = run - 1; i >= 0; i--) {
+    if ((inf >> i) & 1) continue;
+    F zi = mul(suf, pre[i]);  // 1 / z_i
+    suf = mul(suf, zs[i]);
+    const F x = mul(xs[i], sqr(zi));
+    const uint64_t h = dlog_hash<C, F>(x);
+    const unsigned long long v = ((h >> DLOG_JBITS) << DLOG_JBITS) | ((uint64_t)g * run + 1 + i);
+    uint64_t idx = h & mask;
+    for (uint64_t n = 0; n <= mask; n++) {  // (at most B of the 2 B slots are ever taken)
+      if (atomicCAS(&slots[idx], 0ull, v) == 0ull) break;
+      idx = (idx + 1) & mask;
+    }
+  }
+}
+};
+
+// The launch-uniform giant steps: steps[i] = (i + 1) S G, i < K, normalised affine in the internal form
+template <class C, class F>
+__global__ void __launch_bounds__(64, GS_WPE) k_dlog_steps(const uint8_t* base, uint64_t S, int K, Aff<F>* steps) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= K) return;
+  Aff<F> G, R;
+  aff_load<C>(G, base);
+  Jac<F> J;
+  jac_smul_u64(J, G, (uint64_t)(i + 1) * S);
+  jac_to_aff(R, J);
+  steps[i] = R;
+}
+
+// The walk, one lane per point.  This launch covers the centres t0 .. t0 + nsteps - 1.  The lane keeps an affine anchor
+// A = P - (c_t - S) G and takes K giant steps at a time: Q_(t+i-1) = A - M_i, M_i = i S G (launch-uniform, `steps`), all
+// K slopes from ONE inversion of the product of the differences x(M_i) - x(A) (prefix products in LDS), x only; the last
+// of them also gives y and becomes the next anchor.  Per step: 1 (prefix) + 2 (back-substitution) + 1 (slope) + 1
+// (square) multiplications, + 1 for the canonical form that is hashed.
+//   * x(M_i) = x(A): Q = O (x is the centre itself) or a doubling.  The difference is replaced by one so that the
+//     shared product stays invertible, the step is flagged, the centre goes to the confirmation, no lookup.
+//   * a hit gives the candidates c_t + j and c_t - j (only x is stored); each candidate inside [0, 2^bits) is confirmed
+//     by x G == P.  Nothing is reported unconfirmed: a false hit, a wrong base, a point outside <G> cost time only.
+//   * lanes that are done keep computing (the wave is in lockstep) but read and write nothing.
+template <class C, class F>
+struct k_dlog {
+  static __device__ __forceinline__ void hit(bool& done, size_t g, const Aff<F>& G, const Aff<F>& P, int64_t x,
+                                            unsigned bits, Fr<C>* out, uint8_t* found) {
+    if (done || x < 0 || x >= ((int64_t)1 << bits)) return;
+    if (!dlog_confirm<C, F>(G, P, (uint64_t)x)) return;
+    Fr<C> k = fzero<FrM<C>>();
+    k.v[0] = (uint32_t)x;
+    k.v[1] = (uint32_t)((uint64_t)x >> 32);
+    out[g] = to_mont(k);
+    found[g] = 1;
+    done = true;
+  }
+  static __device__ __forceinline__ void run(size_t g, size_t total, const uint8_t* pts, const uint8_t* base,
+                                            const Aff<F>* steps, const unsigned long long* slots, unsigned log2_slots,
+                                            unsigned log2_table, unsigned bits, unsigned fp_bits, uint64_t t0,
+                                            uint32_t nsteps, int first, Fr<C>* out, uint8_t* found) {
+  typedef DlogShape<F> SH;
+  constexpr int K = SH::K, NW = SH::NW;
+  __shared__ limb_t pre_s[K * NW * 64];
+  limb_t* const mine = pre_s + (threadIdx.x & 63);
+  const uint64_t B = (uint64_t)1 << log2_table, S = 2 * B;
+  const uint64_t mask = ((uint64_t)1 << log2_slots) - 1, fpm = ((uint64_t)1 << fp_bits) - 1;
+  bool done = g >= total;
+  Aff<F> G, P;
+  aff_load<C>(G, base);
+  P = G;
+  if (!done) {
+    aff_load<C>(P, pts + g * AFFB(C, F));
+    if (first) {
+      const bool o = aff_is_inf(P);  // P = O: x = 0
+      out[g] = fzero<FrM<C>>();
+      found[g] = o ? 1 : 0;
+      done = o;
+    } else {
+      done = found[g] != 0;
+    }
+  }
+  // the anchor of the first block: P - (c_t0 - S) G = P + B G for t0 = 0
+  Aff<F> A;
+  {
+    Jac<F> J;
+    jac_smul_u64(J, G, t0 == 0 ? B : B + (t0 - 1) * S);
+    if (t0 != 0) J.y = neg(J.y);
+    jac_madd_edge(J, J, P);
+    jac_to_aff(A, J);
+    if (aff_is_inf(A)) done = true;  // x = c_(t0-1) (an earlier launch has reported it) or x = -B: not in range
+  }
+  uint32_t s = 0;
+#pragma unroll 1
+  while (s < nsteps) {
+    if (__ballot(!done) == 0) break;
+    const int kb = nsteps - s < (uint32_t)K ? (int)(nsteps - s) : K;  // launch-uniform
+    F acc = one_of<F>();
+    uint32_t zf = 0;
+#pragma unroll 1
+    for (int i = 1; i <= kb; i++) {
+      F mx;
+      ld_limbs(mx, &steps[i - 1].x);
+      F d = norm(sub(mx, A.x));
+      if (gz_is_zero<C>(d)) {
+        zf |= 1u << i;
+        d = one_of<F>();
+      }
+#pragma unroll
+      for (int q = 0; q < NW; q++) mine[((i - 1) * NW + q) * 64] = reinterpret_cast<const limb_t*>(&acc)[q];
+      acc = mul(acc, d);
+    }
+    F suf = inv(acc);
+    Aff<F> An = A;
+#pragma unroll 1
+    for (int i = kb; i >= 1; i--) {
+      F mx, my, pre;
+      ld_limbs(mx, &steps[i - 1].x);
+      ld_limbs(my, &steps[i - 1].y);
+#pragma unroll
+      for (int q = 0; q < NW; q++) reinterpret_cast<limb_t*>(&pre)[q] = mine[((i - 1) * NW + q) * 64];
+      const bool z = ((zf >> i) & 1) != 0;
+      F d = norm(sub(mx, A.x));
+      if (z) d = one_of<F>();
+      const F id = mul(suf, pre);  // 1 / (x(M_i) - x(A))
+      suf = mul(suf, d);
+      const F lam = mul(norm(sub(neg(my), A.y)), id);  // the chord through A and -M_i
+      const F x3 = norm(sub(sub(sqr(lam), A.x), mx));
+      if (i == K) {
+        An.x = x3;
+        An.y = norm(sub(mul(lam, norm(sub(A.x, x3))), A.y));
+      }
+      const uint64_t h = dlog_hash<C, F>(x3);
+      const int64_t c = (int64_t)(B + (t0 + s + (uint64_t)(i - 1)) * S);
+      if (done) continue;
+      if (z) {
+        hit(done, g, G, P, c, bits, out, found);
+        continue;
+      }
+      const uint64_t fp = h >> DLOG_JBITS;
+      uint64_t idx = h & mask;
+      for (uint64_t n = 0; n <= mask && !done; n++) {  // to the first empty slot
+        const unsigned long long v = slots[idx];
+        if (v == 0) break;
+        if ((((v >> DLOG_JBITS) ^ fp) & fpm) == 0) {
+          const int64_t j = (int64_t)(v & (((uint64_t)1 << DLOG_JBITS) - 1));
+          hit(done, g, G, P, c + j, bits, out, found);
+          hit(done, g, G, P, c - j, bits, out, found);
+        }
+        idx = (idx + 1) & mask;
+      }
+    }
+    if (kb == K) {
+      if ((zf >> K) & 1) {  // A = +-M_K: the next anchor is O or 2 A, by the complete formulas
+        Jac<F> J;
+        jac_from_aff(J, A);
+        Aff<F> m = steps[K - 1];
+        m.y = neg(m.y);
+        jac_madd_edge(J, J, m);
+        jac_to_aff(An, J);
+        if (aff_is_inf(An)) done = true;  // P = c G exactly and the centre c has just been tried
+      }
+      A = An;
+    }
+    s += (uint32_t)kb;
+  }
+}
+};
+
 // window tables: tab[(b*32 + w)*256 + d] = d * 2^(8w) * base[b]   (d = 0 -> identity)
 template <class C, class F>
 __global__ void __launch_bounds__(64, GS_WPE) k_build_tables(int nb, const uint8_t* bases, Aff<F>* tab) {

@@ -10,6 +10,7 @@ top of the C ABI (same names, argument meaning and error behaviour):
         .verify(com_proof, crs) -> bool                                    src/verifier.rs:18-21
     rerandomize(equ, com_proof, crs, rng) -> CProof                      (new) fresh commitments and proof, no witness
     generate_crs_with_key -> (CRS, key), extract(commit, crs, key)        (new) open commitments with the binding key
+    extract_scalars(commit, crs, key, bits, log2_table=None)              (new) committed scalars < 2^bits back themselves
     EquProof {pi, theta, equ_type, rand}, CProof {xcoms, ycoms, equ_proofs} prove.rs:55-69
 
 Values are numpy uint64 limb arrays in the boundary layout of include/gs_amd.h
@@ -82,6 +83,29 @@ def extract(commit, crs, key):
         return []
     out = crs.engine.extract(group, _cat(commit.coms, 0))
     return [out[i].view(np.uint64).copy() for i in range(n)]
+
+
+def extract_scalars(commit, crs, key, bits, log2_table=None):
+    """The scalars a Commit1 / Commit2 of batch_commit_scalar_to_B1 / _B2 binds, opened with the binding key of `crs`:
+    a list with the Fr (Montgomery limbs, as it was committed) of every scalar below 2^bits and None where there is none
+    (gs_extract_scalar_b1 / _b2: extraction, then a baby-step giant-step walk from the image x * generator back to x).
+    The baby-step table of the group, 2^log2_table multiples of crs.g1_gen / crs.g2_gen, is built unless the last
+    dlog_prepare of crs.engine for the group was for exactly this base and size (Engine.dlog_prepare records both);
+    log2_table = None picks about half of bits (at most 24, at least 2 and what keeps a lane's walk below 2^24 steps),
+    so calls that alternate between values of bits rebuild the table unless they pass one log2_table.  Raises GsError
+    as extract does."""
+    group = 2 if isinstance(commit, Commit2) else 1
+    crs.engine.set_extraction_key(key)
+    if log2_table is None:
+        log2_table = max(2, min(24, (bits + 1) // 2), bits - 25)
+    base = crs.g1_gen if group == 1 else crs.g2_gen
+    if crs.engine.dlog_table(group) != (np.ascontiguousarray(base).view(np.uint8).tobytes(), int(log2_table)):
+        crs.engine.dlog_prepare(group, base, log2_table)
+    n = len(commit.coms)
+    if n == 0:
+        return []
+    xs, found = crs.engine.extract_scalar(group, _cat(commit.coms, 0), bits)
+    return [xs[i].view(np.uint64).copy() if found[i] else None for i in range(n)]
 
 
 class Commit1:

@@ -103,6 +103,9 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  *                   accumulator pair and the verdict are those of endo = 1.
  *   "mixed_merge"  -1 planned (merged up to 2^14 equations per call on a 256-CU device) | 0 the parts of a mixed call run
  *                   one after the other | 1 their launches are merged
+ *   "dlog_steps"    0 = 2^15 (an estimate) | giant steps one k_dlog launch walks; longer walks are several launches
+ *   "dlog_fp_bits"  0 = all 35 | 1 .. 35 fingerprint bits a lookup of gs_dlog_* compares (small values force false hits,
+ *                   which the confirmation rejects).  Both are test knobs without an environment twin.
  * The same knobs are read ONCE at gs_ctx_create from the environment for experiments without recompiling the caller:
  * GS_MILLER_TWIN, GS_MILLER_CH, GS_VAR_TM, GS_VAR_MO, GS_VAR_W, GS_VAR_W2, GS_RED_K, GS_COOP_FE, GS_LINE_TABLES, GS_OVERLAP,
  * GS_ENDO (same values).
@@ -252,7 +255,7 @@ int gs_rerandomize_statement(gs_ctx*, int equ_type, size_t E, int m, int n, cons
  * ANY commitment to the witness it binds:
  *   G1 variable  c = (O, X) + r0 u0 + r1 u1  ->  c.1 - a1 c.0 = X
  *   Fr variable  c = x W1 + r u0             ->  c.1 - a1 c.0 = x p1   (the witness's IMAGE: recovering x from it is a
- *                                                 discrete logarithm, which nothing here attempts)
+ *                                                 discrete logarithm: gs_extract_scalar_* below, for short x)
  * and likewise in G2 with a2.  On the hiding key (gs_crs_generate_hiding) u1.1 = t1 a1 p1 - p1 and nothing can be
  * extracted; that key is refused.
  *
@@ -277,6 +280,48 @@ int gs_extract_g1_dev(gs_ctx*, size_t count, const void* coms_com1, void* out_g1
 int gs_extract_g2_dev(gs_ctx*, size_t count, const void* coms_com2, void* out_g2);
 int gs_extract_g1(gs_ctx*, size_t count, const void* coms_com1, void* out_g1);
 int gs_extract_g2(gs_ctx*, size_t count, const void* coms_com2, void* out_g2);
+
+/* ---- dlog (bounded scalar witnesses back from their images) --------------- */
+/* gs_extract_* opens a committed SCALAR to its image x * generator.  The scalars committed under Groth-Sahai (amounts,
+ * votes, attribute values, indices) are short; these calls recover x in [0, 2^bits) by baby-step giant-step:
+ *   found[i] = 1, out[i] = x_i   when 0 <= x_i < 2^bits with x_i * base == pts[i] exists; out is an Fr in the form
+ *                                gs_commit_fr_b1 takes, so an opened commitment returns the bytes that were committed
+ *   found[i] = 0, out[i] = 0     otherwise
+ * The answer is exact: a reported x has been confirmed by x * base == pts[i] on full coordinates.  pts may be ANY curve
+ * points: one outside <base> (a cofactor component, say) gives found = 0.  An input off the curve has an undefined
+ * verdict, but every loop is bounded and the call returns.
+ *
+ * gs_dlog_prepare builds the baby-step table j * base, j = 1 .. 2^log2_table, for group 1 (G1) or 2 (G2) on the device:
+ * base_host is a HOST pointer to one affine point.  One table per group per context; a second call for the group
+ * replaces the table (the old one is freed first), gs_ctx_destroy frees them.  The table is PUBLIC data: it is not
+ * tied to the CRS and gs_set_crs leaves it alone.  MEMORY: 2^(log2_table + 1) slots of 8 bytes (load factor <= 1/2),
+ * i.e. 256 MB at log2_table = 24.  GS_ERR_ARG for the identity as base, a group other than 1 | 2 or log2_table outside
+ * [2, 28]; GS_ERR_ALLOC when the table does not fit.  The call synchronises the stream.  The base is meant to generate
+ * the group the points live in (the CRS generator: prime order r).  A base of SMALL order is accepted, but multiples
+ * i * 2^(log2_table+1) * base of the walk that fall on the identity are not treated specially, so found may be 0 for an
+ * x that exists; a reported x is still always a confirmed one.
+ * Kernel profile names (gs_prof_get): "k_dlog_table.g1|g2" and "k_dlog_steps.g1|g2" once per gs_dlog_prepare (the
+ * baby-step table and the few launch-uniform giant steps), "k_dlog.g1|g2" once per launch of the walk.
+ *
+ * gs_dlog_g1 / gs_dlog_g2 (host pointers) and their _dev forms (device pointers, enqueued on the context's stream
+ * without synchronising): a lane walks 2^(bits - log2_table - 1) giant steps at worst, about 6 Fq multiplications each
+ * in G1.  GS_ERR_ARG when no table is prepared for the group, when bits is outside [1, 48], when
+ * bits > log2_table + 25 (more than 2^24 giant steps per lane: gs_last_error names the table size that is needed),
+ * when out_fr, found_u8 and the input overlap, and inside a mixed call.  count = 0 is a no-op.
+ *
+ * gs_extract_scalar_b1 / _b2: gs_extract_g1 / _g2 into context scratch, then the walk over the images.  Needs the
+ * extraction key (refusals as gs_extract_*) and a table prepared for the group with the CRS generator (g1_gen /
+ * g2_gen) as base; with any other base the confirmation gives found = 0, never a wrong x.
+ * The multi-GPU handles (gs_multi_*) have no counterpart of these calls: use a shard's context (gs_multi_ctx). */
+int gs_dlog_prepare(gs_ctx*, int group /* 1 | 2 */, const void* base_host, unsigned log2_table);
+int gs_dlog_g1_dev(gs_ctx*, size_t count, const void* pts_g1, unsigned bits, void* out_fr, void* found_u8);
+int gs_dlog_g2_dev(gs_ctx*, size_t count, const void* pts_g2, unsigned bits, void* out_fr, void* found_u8);
+int gs_dlog_g1(gs_ctx*, size_t count, const void* pts_g1, unsigned bits, void* out_fr, void* found_u8);
+int gs_dlog_g2(gs_ctx*, size_t count, const void* pts_g2, unsigned bits, void* out_fr, void* found_u8);
+int gs_extract_scalar_b1_dev(gs_ctx*, size_t count, const void* coms_com1, unsigned bits, void* out_fr, void* found_u8);
+int gs_extract_scalar_b2_dev(gs_ctx*, size_t count, const void* coms_com2, unsigned bits, void* out_fr, void* found_u8);
+int gs_extract_scalar_b1(gs_ctx*, size_t count, const void* coms_com1, unsigned bits, void* out_fr, void* found_u8);
+int gs_extract_scalar_b2(gs_ctx*, size_t count, const void* coms_com2, unsigned bits, void* out_fr, void* found_u8);
 
 /* ---- verify (src/verifier.rs) ------------------------------------------- */
 /* ok[i] = 1 iff equation i verifies; exact reference semantics (four GT cell

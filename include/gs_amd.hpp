@@ -14,6 +14,7 @@
 //     .verify(com_proof, crs) -> bool             src/verifier.rs:18-21   (Verifiable)
 //   EquProof {pi, theta, equ_type, rand}, CProof  src/prover/prove.rs:55-69
 //   CRS::generate_crs_with_key, CRS::set_extraction_key, CRS::extract   (new) open commitments with the binding key
+//   CRS::dlog_prepare, CRS::extract_scalars                             (new) committed scalars < 2^bits back themselves
 //
 // Values are byte strings in the boundary layout of gs_amd.h (arkworks' Montgomery
 // limbs).  `Rng` is any type with `Fr fr()`; draws happen in the reference's order
@@ -23,6 +24,7 @@
 #include <cstdint>
 #include <cstring>
 #include <memory>
+#include <optional>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -163,6 +165,21 @@ struct CRS {  // generator.rs:35-42
   std::vector<G2Affine> extract(const std::vector<Com2>& coms) const {
     return extract_impl<G2Affine>(coms, 2 * ctx->sz[3], ctx->sz[3], gs_extract_g2);
   }
+  // (new) Build the baby-step table of `group` (1: G1, 2: G2) over this CRS's generator (gs_dlog_prepare):
+  // 2^log2_table entries in 2^(log2_table + 1) slots of 8 bytes on the device.  A second call replaces the table.
+  void dlog_prepare(int group, unsigned log2_table) const {
+    if (group != 1 && group != 2) throw Panic("assertion failed: group is 1 or 2");
+    ctx->chk(gs_dlog_prepare(ctx->c, group, group == 1 ? g1_gen.v.data() : g2_gen.v.data(), log2_table));
+  }
+  // (new) The scalars the commitments of batch_commit_scalar_to_B1 / _B2 bind, opened with the installed key and walked
+  // back from their images (gs_extract_scalar_b1 / _b2): the committed Fr where it is below 2^bits, nothing where it
+  // is not.  Needs set_extraction_key and dlog_prepare for the group; bits <= log2_table + 25.
+  std::vector<std::optional<Fr>> extract_scalars(const std::vector<Com1>& coms, unsigned bits) const {
+    return extract_scalars_impl(coms, 2 * ctx->sz[2], bits, gs_extract_scalar_b1);
+  }
+  std::vector<std::optional<Fr>> extract_scalars(const std::vector<Com2>& coms, unsigned bits) const {
+    return extract_scalars_impl(coms, 2 * ctx->sz[3], bits, gs_extract_scalar_b2);
+  }
 
  private:
   template <class Rng> static Bytes draw_scalars(Rng& rng) {
@@ -201,6 +218,21 @@ struct CRS {  // generator.rs:35-42
     Bytes in = cat(coms), out(coms.size() * pt_sz);
     ctx->chk(fn(ctx->c, coms.size(), in.data(), out.data()));
     return split<P>(out, coms.size());
+  }
+  template <class Com, class F>
+  std::vector<std::optional<Fr>> extract_scalars_impl(const std::vector<Com>& coms, size_t com_sz, unsigned bits,
+                                                      F fn) const {
+    for (const Com& c : coms) assert_eq(c.v.size(), com_sz, "commitment size");
+    if (coms.empty()) {  // (the key and the table are still asked for)
+      ctx->chk(fn(ctx->c, 0, nullptr, bits, nullptr, nullptr));
+      return {};
+    }
+    Bytes in = cat(coms), out(coms.size() * 32), found(coms.size());
+    ctx->chk(fn(ctx->c, coms.size(), in.data(), bits, out.data(), found.data()));
+    std::vector<std::optional<Fr>> o(coms.size());
+    for (size_t i = 0; i < coms.size(); i++)
+      if (found[i]) o[i] = Fr{Bytes(out.begin() + 32 * i, out.begin() + 32 * (i + 1))};
+    return o;
   }
 };
 

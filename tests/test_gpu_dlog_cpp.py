@@ -1,0 +1,39 @@
+"""The C++ host layer's scalar extraction (include/gs_amd.hpp: CRS::dlog_prepare, CRS::extract_scalars) driven by
+tests/cpp/test_dlog.cpp: built with g++ -Werror against the in-tree libgs_amd.so and run on the GPU, on the generators
+of a golden PairingProduct case of each curve."""
+import os
+import subprocess
+
+import pytest
+
+from gsutil import HERE, REPO, curve
+
+pytestmark = pytest.mark.gpu
+
+
+def build_program():
+    from test_gpu_cpp_host import BUILD, LIBDIR
+
+    os.makedirs(BUILD, exist_ok=True)
+    exe = os.path.join(BUILD, "test_dlog")
+    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Werror", "-I" + os.path.join(REPO, "include"),
+           os.path.join(HERE, "cpp", "test_dlog.cpp"), "-o", exe, "-L" + LIBDIR, "-lgs_amd",
+           "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,/opt/rocm/lib"]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+@pytest.mark.parametrize("name", ["bls12_381", "bn254"])
+def test_cpp_extract_scalars(name, tmp_path):
+    from test_gpu_cpp_host import write_case
+
+    exe = build_program()
+    c = curve(name)
+    case = next(k for k in c.golden["cases"] if k["type"] == 0)
+    p = str(tmp_path / (case["name"] + ".bin"))
+    write_case(c, case, p)
+    scalars = [0, 7, 54321, 1 << 16]  # three inside [0, 2^16), the last one outside
+    hexes = [c.fr(x).tobytes().hex() for x in scalars]
+    r = subprocess.run([exe, p] + hexes, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and r.stdout.startswith("OK"), (case["name"], r.stdout, r.stderr)
