@@ -155,6 +155,32 @@ template <class C> struct Twin {
     jac_to_aff(R, J);
     stg2(o, R);
   }
+  // The digit streams of n CANONICAL scalars (8 words each) as the Straus lanes and shared_digits form them
+  // (endo_digits<C, W>): dg = n x NS x nd(W) signed digits, sgn = n x NS stream signs.  Returns nd(W).
+  template <class F, int W> static int endo_digits_n(int n, const uint32_t* ks, int8_t* dg, uint8_t* sgn) {
+    typedef EndoShape<C, F> E;
+    constexpr int ND = E::nd(W);
+    for (int i = 0; i < n; i++) {
+      Fr<C> k;
+      memcpy(&k, ks + (size_t)i * C::NR, sizeof k);
+      gs::endo_digits<C, W>(dg + (size_t)i * E::NS * ND, sgn + (size_t)i * E::NS, k, (const Jac<F>*)nullptr);
+    }
+    return ND;
+  }
+  static int digit_streams(int group, int w, int n, const uint32_t* ks, int8_t* dg, uint8_t* sgn) {
+    if (group == 1) return w == 5 ? endo_digits_n<F1, 5>(n, ks, dg, sgn) : endo_digits_n<F1, 4>(n, ks, dg, sgn);
+    return w == 5 ? endo_digits_n<F2, 5>(n, ks, dg, sgn) : endo_digits_n<F2, 4>(n, ks, dg, sgn);
+  }
+  // recode_w4 on the whole scalar (the plain path, jac_smul): n x ND digits.  Returns ND.
+  static int recode_plain(int n, const uint32_t* ks, int8_t* dg) {
+    constexpr int ND = (FrM<C>::BITS + 3) / 4 + 1;
+    for (int i = 0; i < n; i++) {
+      Fr<C> k;
+      memcpy(&k, ks + (size_t)i * C::NR, sizeof k);
+      recode_w4<FrM<C>>(dg + (size_t)i * ND, ND, k);
+    }
+    return ND;
+  }
   static void g1_add(const uint8_t* p, const uint8_t* q, uint8_t* o) {
     Aff<F1> P = ldg1(p), Q = ldg1(q), R;
     Jac<F1> J, K;
@@ -503,6 +529,10 @@ extern "C" long twin_fq_mul_count(int reset) {
   void twin_g2_smul_##SUF(const uint8_t* p, const uint32_t* k, uint8_t* o) { Twin<CURVE>::g2_smul(p, k, o); }    \
   void twin_g1_msm_##SUF(int nt, const uint8_t* p, const uint32_t* k, uint8_t* o) { Twin<CURVE>::g1_msm(nt, p, k, o); } \
   void twin_g2_msm_##SUF(int nt, const uint8_t* p, const uint32_t* k, uint8_t* o) { Twin<CURVE>::g2_msm(nt, p, k, o); } \
+  int twin_endo_digits_##SUF(int g, int w, int n, const uint32_t* k, int8_t* dg, uint8_t* sgn) {                  \
+    return Twin<CURVE>::digit_streams(g, w, n, k, dg, sgn);                                                         \
+  }                                                                                                               \
+  int twin_recode_w4_##SUF(int n, const uint32_t* k, int8_t* dg) { return Twin<CURVE>::recode_plain(n, k, dg); }  \
   void twin_g1_add_##SUF(const uint8_t* p, const uint8_t* q, uint8_t* o) { Twin<CURVE>::g1_add(p, q, o); }       \
   void twin_g1_to_aff_##SUF(const uint8_t* p, uint8_t* o) { Twin<CURVE>::g1_to_aff(p, o); }                       \
   void twin_g2_madd_##SUF(const uint8_t* p, const uint8_t* q, uint8_t* o) { Twin<CURVE>::g2_madd(p, q, o); }     \
