@@ -218,7 +218,12 @@ def test_bench_plain_line_and_dumped_outputs(tmp_path):
 def test_edge_values_against_c_oracle(cname, cid, ty):
     """Degenerate inputs the reference accepts silently: identity witnesses / constants, zero and r-1 scalars, zero
     Gamma rows, no randomness at all, repeated points.  Outputs must still equal the C restatement bit for bit and
-    the verdicts (true or false -- the targets are no longer satisfied) must agree."""
+    the verdicts (true or false -- the targets are no longer satisfied) must agree.
+
+    The witnesses are patched and the targets kept, so the patched equations 0, 1, 3 and 4 are FALSE statements (the
+    oracle's verdict on them is 0; equation 2, without randomness, keeps a satisfied target): a verifier that mishandles
+    an identity answers 0 there as well, and this test cannot tell the two apart.  Degenerate equations that are TRUE
+    statements, under every forced kernel shape, are in tests/test_gpu_sparse.py (batch: tests/sparsevec.py)."""
     import torch
 
     import groth_sahai_rs_amd as gs

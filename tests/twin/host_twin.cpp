@@ -403,16 +403,22 @@ template <class C> struct Twin {
     static long v = 0;
     return v;
   }
-  // the same with the pairs selected by `mask` reading a precomputed line table of their G2 argument
-  static void multi_pairing_fixed(int np, const uint8_t* ps, const uint8_t* qs, unsigned mask, uint8_t* o, int twin_mode) {
+  // the same with the pairs selected by `mask` reading a precomputed line table of their G2 argument.  p1s: the G1
+  // arguments of the second accumulator in the twin modes (the a = 1 components of the triples; multi_pairing_fixed
+  // hands the same array to both, multi_pairing_two distinct ones -- identities included, so that the two components
+  // of a triple can differ in being live)
+  static void multi_pairing_fixed(int np, const uint8_t* ps, const uint8_t* p1s, const uint8_t* qs, unsigned mask, uint8_t* o,
+                                  int twin_mode) {
     constexpr int NLN = miller_line_count<C>();
     Aff<F1>* P = new Aff<F1>[np];
+    std::vector<Aff<F1>> P1(np);
     Aff<F2>* Q = new Aff<F2>[np];
     Proj2<C>* T = new Proj2<C>[np];
     Line<C>* tabs = new Line<C>[np * NLN];
     const Line<C>** fx = new const Line<C>*[np];
     for (int i = 0; i < np; i++) {
       P[i] = ldg1(ps + i * 2 * NB);
+      P1[i] = ldg1(p1s + i * 2 * NB);
       Q[i] = ldg2(qs + i * 4 * NB);
       fx[i] = nullptr;
       if ((mask >> i) & 1) {
@@ -432,16 +438,18 @@ template <class C> struct Twin {
       const int nstep = (int)ord.size();
       for (int i = 0; i < np; i++)
         if ((mask >> i) & 1) ord.push_back(i);
-      std::vector<Aff<F1>> Pp(np);
+      std::vector<Aff<F1>> Pp[2] = {std::vector<Aff<F1>>(np), std::vector<Aff<F1>>(np)};  // each lane's OWN component
       std::vector<const Line<C>*> fxp(np);
       std::vector<Aff<F2>> qo[2];
       uint32_t qok = 0;
       for (int k = 0; k < np; k++) {
-        Pp[k] = P[ord[k]];
+        Pp[0][k] = P[ord[k]];
+        Pp[1][k] = P1[ord[k]];
         fxp[k] = fx[ord[k]];
         if (!aff_is_inf(Q[ord[k]])) qok |= 1u << k;
         if (k < nstep) qo[k & 1].push_back(Q[ord[k]]);
       }
+      if (nstep & 1) qo[1].push_back(Q[ord[nstep - 1]]);  // as k_miller_pair: lane 1 steps a copy, never consumed
       for (int a = 0; a < 2; a++) qo[a].resize((nstep + 1) / 2 + 1);
       struct Exchange {
         Line<C> slot[2];
@@ -472,14 +480,14 @@ template <class C> struct Twin {
         th[a] = std::thread([&, a] {
           Lane x{&ex, a};
           std::vector<Proj2<C>> ts((nstep + 1) / 2 + 1);
-          multi_miller_pair(acc[a], a, Pp.data(), qo[a].data(), qok, nstep, np, ts.data(), fxp.data(), x);
+          multi_miller_pair(acc[a], a, Pp[a].data(), qo[a].data(), qok, nstep, np, ts.data(), fxp.data(), x);
         });
       for (int a = 0; a < 2; a++) th[a].join();
       f = acc[0];
       f1 = acc[1];
     } else if (twin_mode) {
       uint8_t* live = new uint8_t[np];
-      multi_miller2(f, f1, P, P, Q, np, T, live, fx);
+      multi_miller2(f, f1, P, P1.data(), Q, np, T, live, fx);
       delete[] live;
     } else {
       bool* live = new bool[np];
@@ -551,7 +559,13 @@ extern "C" long twin_fq_mul_count(int reset) {
   void twin_exp_by_x_##SUF(const uint8_t* in, uint8_t* out) { Twin<CURVE>::exp_by_x(in, out); }                   \
   void twin_multi_pairing_fixed_##SUF(int np, const uint8_t* ps, const uint8_t* qs, unsigned mask, uint8_t* o,     \
                                       int twin_mode) {                                                           \
-    Twin<CURVE>::multi_pairing_fixed(np, ps, qs, mask, o, twin_mode);                                              \
+    Twin<CURVE>::multi_pairing_fixed(np, ps, ps, qs, mask, o, twin_mode);                                          \
+  }                                                                                                               \
+  /* the twin (mode 1) and the lane-pair (mode 2) loop on DISTINCT component arrays p0s, p1s; o = both accumulators */ \
+  /* after the final exponentiation                                                                            */ \
+  void twin_multi_pairing_two_##SUF(int np, const uint8_t* p0s, const uint8_t* p1s, const uint8_t* qs,            \
+                                    unsigned mask, uint8_t* o, int twin_mode) {                                   \
+    Twin<CURVE>::multi_pairing_fixed(np, p0s, p1s, qs, mask, o, twin_mode);                                        \
   }                                                                                                               \
   void twin_multi_pairing_##SUF(int np, const uint8_t* ps, const uint8_t* qs, uint8_t* o, int fe) {              \
     Twin<CURVE>::multi_pairing(np, ps, qs, o, fe);                                                                \
