@@ -21,6 +21,7 @@ SYMBOLS = [
     "gs_commit_g1", "gs_commit_g2", "gs_commit_fr_b1", "gs_commit_fr_b2",
     "gs_prove_batch_dev", "gs_prove_batch", "gs_verify_batch_dev", "gs_verify_batch",
     "gs_verify_batch_rlc_dev", "gs_verify_batch_rlc", "gs_gt_finalize",
+    "gs_verify_statements_rlc_dev", "gs_verify_statements_rlc",
     "gs_prove_statement_dev", "gs_prove_statement", "gs_verify_statement_dev", "gs_verify_statement",
     "gs_mat_left_mul_com1", "gs_mat_left_mul_com2", "gs_pairing_sum", "gs_fr_matmul",
     "gs_g1_mul_batch", "gs_g2_mul_batch", "gs_g1_mul_batch_dev", "gs_g2_mul_batch_dev",
@@ -459,6 +460,33 @@ class Engine:
                                                _p(ok)))
         return int(ok[0]), acc
 
+    def _check_statements(self, fn, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc=None,
+                          ok=None):
+        """Byte lengths of S statements of E equations: S copies of a Statement's (shared) layout with N = E."""
+        if S < 1 or E < 1:
+            raise GsError(3, "%s: S and E must be >= 1" % fn)
+        if not (0 <= ty <= 3) or m < 1 or n < 1:
+            raise GsError(1, "%s: bad equation type or empty variable list" % fn)
+        one = self._sizes(ty, E, m, n, True)
+        arrays = dict(A=A, B=B, Gamma=Gamma, target=target, xcoms=xcoms, ycoms=ycoms, pi=pi, theta=theta)
+        _need(fn, [(k, a, S * one[k]) for k, a in arrays.items()] +
+              [("rho", rho, S * E * 32), ("acc", acc, S * 2 * self.GT), ("ok", ok, S)])
+
+    def verify_statements_rlc(self, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
+        """Batched verifier for S statements of E equations each over shared commitments (host buffers; the arrays
+        of statement s are what verify_statement takes, at offset s).  rho: uint64[S*E*4], non-zero, from a CSPRNG
+        (the rho contract of gs_amd.h).  Returns (ok[S], acc[S][2] GT bytes)."""
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        self._check_statements("gs_verify_statements_rlc", ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi,
+                               theta, rho)
+        acc = self._out(S * 2 * self.GT)
+        ok = np.zeros(S, dtype=np.uint8)
+        self._chk(self.lib.gs_verify_statements_rlc(self.ctx, ty, ctypes.c_size_t(S), ctypes.c_size_t(E), m, n, _p(A),
+                                                    _p(B), _p(Gamma), _p(target), _p(xcoms), _p(ycoms), _p(pi),
+                                                    _p(theta), _p(rho), _p(acc), _p(ok)))
+        return ok, acc.reshape(S, 2, self.GT)
+
     def gt_finalize_dev(self, accs_dev, count):
         """the same with `count` pairs in device memory (torch tensor)."""
         _need("gs_gt_finalize_dev", [("accs", accs_dev, count * 2 * self.GT)])
@@ -556,6 +584,16 @@ class Engine:
         self._chk(self.lib.gs_verify_batch_rlc_dev(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
                                                    _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho),
                                                    _p(acc)))
+
+    def verify_statements_rlc_dev(self, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok):
+        """Device form: rho uint64[S*E*4], acc S accumulator pairs, ok S bytes, all on the device (asynchronous)."""
+        self._check_statements("gs_verify_statements_rlc_dev", ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi,
+                               theta, rho, acc, ok)
+        if acc is None or ok is None:
+            raise GsError(3, "gs_verify_statements_rlc_dev: acc and ok are required")
+        self._chk(self.lib.gs_verify_statements_rlc_dev(self.ctx, ty, ctypes.c_size_t(S), ctypes.c_size_t(E), m, n,
+                                                        _p(A), _p(B), _p(Gamma), _p(target), _p(xcoms), _p(ycoms),
+                                                        _p(pi), _p(theta), _p(rho), _p(acc), _p(ok)))
 
     def g_mul_batch_dev(self, group, n, points, broadcast, scalars, out):
         fn = self.lib.gs_g1_mul_batch_dev if group == 1 else self.lib.gs_g2_mul_batch_dev

@@ -2363,6 +2363,237 @@ template <class C> struct Impl {
     return GS_OK;
   }
 
+  // Statement-batched verifier: S statements of E equations each over ONE set of commitments per statement.  The
+  // random linear combination is taken ACROSS the equations of a statement before anything is paired (Blazy et al.,
+  // ACNS 2010), so a statement costs 2n + 2m + 2kx + 2ky Miller pairs whatever E is:
+  //   G1 pass (Com1-shaped outputs, component b):
+  //     P_j.b   = sum_e rho_e,1b A_ej + sum_i,a g_ab,ij c_i.a          (sum_a (sum_e rho_e,ab a_ej) W1.a for scalar A)
+  //     PB.b    = sum_i,a (sum_e rho_e,ab b_ei) c_i.a [- sum_e rho_e,1b t_e] [- sum_a (sum_e rho_e,ab t_e) W1.a]
+  //     Th_l.b  = sum_e,a rho_e,ab theta_el.a
+  //   G2 pass (Com2-shaped outputs, component a):
+  //     Q_i.a   = sum_e rho_e,a1 B_ei,   Pi_k.a = sum_e,b rho_e,ab pi_ek.b,   T.a = sum_e rho_e,a1 t_e  (MSMEG2)
+  //   pairs: e(P_j.b, d_j.b)  e(c_i.a, Q_i.a) | e(PB.b, W2.b)  e(-u_k.a, Pi_k.a)  e(-Th_l.b, v_l.b)  [e(-W1.a, T.a)]
+  // The engine's unit is the statement (N := S): array strides are per statement, p_idx runs over (e, j).  Short
+  // (64-bit) and full-size terms go to separate Straus lanes, so the short ones skip their leading windows; outputs
+  // over the same bases (the two components of every output above) share a table build (share_tables).
+  static int verify_stmt_rlc(gs_ctx* c, int ty, size_t S, size_t E_, int m, int n, const void* A, const void* B,
+                             const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                             const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
+    const bool xg = x_is_group(ty), yg = y_is_group(ty);
+    const int kx = xg ? 2 : 1, ky = yg ? 2 : 1, E = (int)E_;
+    RangeGuard rg_all("gs.verify_stmt_rlc");
+    PoolMap pm;
+    memset(&pm, 0, sizeof pm);
+    int o = 0;
+    pm.RH = o; o += 4 * E;
+    pm.GC = o; o += 4 * m * n;
+    pm.AR = o; o += xg ? 0 : 4 * n;
+    pm.BC = o; o += yg ? 0 : 4 * m;
+    pm.NR = o; o += ty == GS_QUAD ? 4 : 0;
+    pm.total = o;
+    const int nout = o;
+    void* pool;
+    RC(scratch(c, "srlc.pool", S * pm.total * sizeof(Fr<C>), &pool));
+    {
+      // one lane per statement while a statement is small; one lane per output scalar (E products each) otherwise
+      // (4 x 4, S E = 2^14, profiles/stmt_rlc/rate_2p14.json: lanes of E products take 0.07 ms at E = 16 and 0.15 ms at
+      // E = 64; one lane per statement walking the 1664 products of an E = 16 statement was an order of magnitude slower)
+      const bool narrow = !wide_prep(m, n) && (size_t)E * (size_t)(4 * m * n + 4 * (m + n) + 8) <= 128;
+      const int per = narrow ? 1 : nout;
+      c->work_hint = S * (uint64_t)E * (uint64_t)(nout - 4 * E + 4);
+      RC(launch(c, "k_prep_verify_stmt_rlc", k_prep_verify_stmt_rlc<C>, S * (size_t)per, 64, S, E, m, n, nout, per,
+                (const Fr<C>*)G, xg ? nullptr : (const Fr<C>*)A, yg ? nullptr : (const Fr<C>*)B,
+                ty == GS_QUAD ? (const Fr<C>*)target : nullptr, rho, pm, (Fr<C>*)pool));
+    }
+    auto RH = [&](int e, int a, int b) { return pm.RH + 4 * e + 2 * a + b; };
+    const int tm = c->endo ? 8 : 1;  // endo = 0: one plain double-and-add lane per term, as everywhere else
+    // ---- G1 pass: elements 0..n-1 = P_j, then [PB], Th_l (ky).  Arrays: 0 xcoms, 1 A, 2 target (MSMEG1), 3 theta
+    const int iPB = n, iTh = n + (yg ? 0 : 1), n1 = iTh + ky;
+    void* s1;
+    RC(scratch(c, "srlc.s1", S * n1 * Z::COM1, &s1));
+    {
+      SidePlan sp;
+      sp.tm = tm;
+      int slot = 0;
+      for (int q = 0; q < n1; q++) {
+        int b0 = slot, e0 = 0, b1 = 0;
+        for (int b = 0; b < 2; b++) {
+          if (b == 1) { e0 = slot; b1 = slot; }
+          std::vector<VarTask> shortt, full;
+          if (q < n) {
+            const int j = q;
+            if (xg)
+              for (int e = 0; e < E; e++) shortt.push_back(mkvar(RH(e, 1, b), 1, e * n + j, 0));
+            else
+              sp.fix.push_back(mkfix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0, slot++));
+            for (int i = 0; i < m; i++)
+              for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.GC + ((2 * a + b) * m + i) * n + j, 0, 2 * i + a, 0));
+          } else if (!yg && q == iPB) {
+            for (int i = 0; i < m; i++)
+              for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.BC + i * 4 + 2 * a + b, 0, 2 * i + a, 0));
+            if (ty == GS_MSMEG1)
+              for (int e = 0; e < E; e++) {
+                VarTask v = mkvar(RH(e, 1, b), 2, e, 0);
+                v.neg = 1;
+                shortt.push_back(v);
+              }
+            if (ty == GS_QUAD) sp.fix.push_back(mkfix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0, slot++));
+          } else {
+            const int l = q - iTh;
+            for (int e = 0; e < E; e++)
+              for (int a = 0; a < 2; a++) shortt.push_back(mkvar(RH(e, a, b), 3, 2 * (e * ky + l) + a, 0));
+          }
+          add_var_terms(sp, shortt, slot);
+          add_var_terms(sp, full, slot);
+        }
+        sp.red.push_back(mkred(b0, e0, b1, slot, 0, q));
+      }
+      sp.nslots = slot;
+      ArrTab arrs;
+      memset(&arrs, 0, sizeof arrs);
+      arrs.base[0] = (const uint8_t*)xcoms;
+      arrs.stride[0] = (uint32_t)(m * Z::COM1);
+      if (xg) {
+        arrs.base[1] = (const uint8_t*)A;
+        arrs.stride[1] = (uint32_t)((size_t)E * n * Z::G1);
+      }
+      if (ty == GS_MSMEG1) {
+        arrs.base[2] = (const uint8_t*)target;
+        arrs.stride[2] = (uint32_t)((size_t)E * Z::G1);
+      }
+      arrs.base[3] = (const uint8_t*)theta;
+      arrs.stride[3] = (uint32_t)((size_t)E * ky * Z::COM1);
+      OutTab outs;
+      memset(&outs, 0, sizeof outs);
+      outs.base[0] = (uint8_t*)s1;
+      outs.stride[0] = (uint32_t)(n1 * Z::COM1);
+      RC((run_side<C, F1>(c, ".s1", S, sp, arrs, (const Fr<C>*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
+    }
+    // ---- G2 pass: elements [Q_i (m)], Pi_k (kx), [T] (MSMEG2).  Arrays: 0 B, 1 pi, 2 target (MSMEG2)
+    const int iPi = yg ? m : 0, iT = iPi + kx, n2 = iT + (ty == GS_MSMEG2 ? 1 : 0);
+    void* s2;
+    RC(scratch(c, "srlc.s2", S * n2 * Z::COM2, &s2));
+    {
+      SidePlan sp;
+      sp.tm = tm;
+      int slot = 0;
+      for (int q = 0; q < n2; q++) {
+        int b0 = slot, e0 = 0, b1 = 0;
+        for (int a = 0; a < 2; a++) {
+          if (a == 1) { e0 = slot; b1 = slot; }
+          std::vector<VarTask> terms;
+          if (q < iPi) {
+            for (int e = 0; e < E; e++) terms.push_back(mkvar(RH(e, a, 1), 0, e * m + q, 0));
+          } else if (q < iT) {
+            const int k = q - iPi;
+            for (int e = 0; e < E; e++)
+              for (int b = 0; b < 2; b++) terms.push_back(mkvar(RH(e, a, b), 1, 2 * (e * kx + k) + b, 0));
+          } else {
+            for (int e = 0; e < E; e++) terms.push_back(mkvar(RH(e, a, 1), 2, e, 0));
+          }
+          add_var_terms(sp, terms, slot);
+        }
+        sp.red.push_back(mkred(b0, e0, b1, slot, 0, q));
+      }
+      sp.nslots = slot;
+      ArrTab arrs;
+      memset(&arrs, 0, sizeof arrs);
+      if (yg) {
+        arrs.base[0] = (const uint8_t*)B;
+        arrs.stride[0] = (uint32_t)((size_t)E * m * Z::G2);
+      }
+      arrs.base[1] = (const uint8_t*)pi;
+      arrs.stride[1] = (uint32_t)((size_t)E * kx * Z::COM2);
+      if (ty == GS_MSMEG2) {
+        arrs.base[2] = (const uint8_t*)target;
+        arrs.stride[2] = (uint32_t)((size_t)E * Z::G2);
+      }
+      OutTab outs;
+      memset(&outs, 0, sizeof outs);
+      outs.base[0] = (uint8_t*)s2;
+      outs.stride[0] = (uint32_t)(n2 * Z::COM2);
+      RC((run_side<C, F2>(c, ".s2", S, sp, arrs, (const Fr<C>*)pool, pm.total, (const A2*)c->tabs->tab16_g2.p, outs)));
+    }
+    // ---- Miller.  P arrays: 0 = S1, 1 = xcoms, 2 = crs G1 (u, W1).  Q arrays: 0 ycoms, 1 = S2, 2 = crs G2 (v, W2)
+    std::vector<PairRef> pr;
+    for (int b = 0; b < 2; b++) {
+      for (int j = 0; j < n; j++) add_pair(pr, 0, 2 * j + b, 0, 0, 2 * j + b);            // (P_j.b, d_j.b)
+      if (!yg) add_pair(pr, 0, 2 * iPB + b, 0, 2, 4 + b);                                 // (PB.b, W2.b)
+      for (int l = 0; l < ky; l++) add_pair(pr, 0, 2 * (iTh + l) + b, 1, 2, 2 * l + b);   // (-Th_l.b, v_l.b)
+    }
+    for (int a = 0; a < 2; a++) {
+      if (yg)
+        for (int i = 0; i < m; i++) add_pair(pr, 1, 2 * i + a, 0, 1, 2 * i + a);          // (c_i.a, Q_i.a)
+      for (int k = 0; k < kx; k++) add_pair(pr, 2, 2 * k + a, 1, 1, 2 * (iPi + k) + a);   // (-u_k.a, Pi_k.a)
+      if (ty == GS_MSMEG2) add_pair(pr, 2, 4 + a, 1, 1, 2 * iT + a);                      // (-W1.a, T.a)
+    }
+    std::vector<MillerTask> mt;
+    {
+      double best = -1;
+      for (double cand : miller_budgets(c, false)) {
+        std::vector<MillerTask> tmp;
+        chunk_tasks(tmp, pr, cand, 0, true, mcost(c->curve, false), c->line_tables);
+        double cost = miller_cost(c, S, tmp, false);
+        if (best < 0 || cost < best) {
+          best = cost;
+          mt = tmp;
+        }
+      }
+    }
+    const MillerTask* dmt;
+    RC(upload(c, "srlc.mt", mt, &dmt));
+    const int ntask = (int)mt.size();
+    void* mpart;
+    RC(scratch(c, "srlc.mpart", S * ntask * sizeof(GT), &mpart));
+    ArrTab parr, qarr;
+    memset(&parr, 0, sizeof parr);
+    memset(&qarr, 0, sizeof qarr);
+    parr.base[0] = (const uint8_t*)s1;
+    parr.stride[0] = (uint32_t)(n1 * Z::COM1);
+    parr.base[1] = (const uint8_t*)xcoms;
+    parr.stride[1] = (uint32_t)(m * Z::COM1);
+    parr.base[2] = (const uint8_t*)c->tabs->crs_g1.p;
+    qarr.base[0] = (const uint8_t*)ycoms;
+    qarr.stride[0] = (uint32_t)(n * Z::COM2);
+    qarr.base[1] = (const uint8_t*)s2;
+    qarr.stride[1] = (uint32_t)(n2 * Z::COM2);
+    qarr.base[2] = (const uint8_t*)c->tabs->crs_g2.p;
+    {
+      const MCost mc = mcost(c->curve, false);
+      double pairs = 0;
+      for (const MillerTask& t : mt)
+        for (int q = 0; q < t.np; q++) pairs += pair_fixed(c->line_tables, t.pr[q]) ? mc.fix / mc.var : 1.0;
+      c->work_hint = (uint64_t)((double)S * pairs);
+    }
+    RC(launch_seg<k_miller<C, false>>(c, "k_miller.srlc", S * ntask, 64, S * ntask, ntask, dmt, parr, qarr, (GT*)mpart, 1,
+              (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+    // ---- PPE: T_s = prod_e t_e^rho_e,11 (segmented K-ary product of k_rlc_tpow's S E powers)
+    const GT* tprod = nullptr;
+    if (ty == GS_PPE) {
+      const int K = 8;
+      void *t0, *t1;
+      RC(scratch(c, "srlc.t0", S * (size_t)E * sizeof(GT), &t0));
+      RC(scratch(c, "srlc.t1", S * (((size_t)E + K - 1) / K) * sizeof(GT), &t1));
+      RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, S * (size_t)E, 64, S * (size_t)E, (const uint8_t*)target, rho, (GT*)t0));
+      GT *in = (GT*)t0, *out = (GT*)t1;
+      for (size_t len = (size_t)E; len > 1;) {
+        size_t lo = (len + K - 1) / K;
+        RC(launch(c, "k_gt_prod_seg", k_gt_prod_seg<C>, S * lo, 64, S, len, (const GT*)in, lo, out, K));
+        std::swap(in, out);
+        len = lo;
+      }
+      tprod = in;
+    }
+    // ---- one final exponentiation per statement: one lane each once that fills the chip, 3-lane groups below that
+    size_t coop_waves = (S + 20) / 21;
+    if (c->coop_fe == 2 || (c->coop_fe == 1 && (fillN(c, S) + 20) / 21 <= c->simd_slots))
+      RC(launch_seg<k_stmt_final_coop<C>>(c, "k_stmt_final.coop", coop_waves * 63, 63, S, ntask, (const GT*)mpart, tprod,
+                (uint8_t*)acc, ok));
+    else
+      RC(launch_seg<k_stmt_final<C>>(c, "k_stmt_final", S, 64, S, ntask, (const GT*)mpart, tprod, (uint8_t*)acc, ok));
+    return GS_OK;
+  }
+
   // accs: count boundary-form pairs (host).  ok = FE(prod accs[i][0]) == prod accs[i][1]
   // accs: `count` interleaved pairs (f_i, t_i) in boundary form, on the host or (dev) on this context's device
   static int gt_finalize(gs_ctx* c, size_t count, const void* accs_host, uint8_t* ok_host, bool dev = false) {
@@ -3796,6 +4027,53 @@ int gs_verify_batch_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A
   RC(st.back(hacc.data(), dacc, hacc.size()));
   if (acc) memcpy(acc, hacc.data(), hacc.size());
   if (ok_all) RC(gs_gt_finalize(c, 1, hacc.data(), ok_all));
+  return GS_OK;
+}
+// ---- statement-batched (RLC) verifier: S statements of E equations over shared commitments ----------------------
+// what the plan cannot index is refused: the engine's arrays are strided per STATEMENT in 32-bit bytes, its task
+// tables and pool offsets are 32-bit
+static int check_stmt_rlc(gs_ctx* c, int ty, size_t S, size_t E, int m, int n) {
+  RC(check_ctx(c, true));
+  RC(check_shape(c, ty, m, n));
+  if (S == 0 || E == 0) return fail(c, GS_ERR_ARG, "empty batch: S and E must be >= 1");
+  const lay::Layout L(sz_fq(c->curve), ty, E, m, n, true);  // one statement = the shared layout with N = E
+  const size_t lim = (size_t)1 << 32;
+  if (E > ((size_t)1 << 20) || L.bytes[lay::A] >= lim || L.bytes[lay::B] >= lim || L.bytes[lay::TARGET] >= lim ||
+      L.bytes[lay::PI] >= lim || L.bytes[lay::THETA] >= lim || L.bytes[lay::XCOMS] >= lim || L.bytes[lay::YCOMS] >= lim ||
+      E * (size_t)(4 + 4 * (m + n)) + 4 * (size_t)m * n * 4 >= ((size_t)1 << 28))
+    return fail(c, GS_ERR_SHAPE, "statement too large for the task tables (E x shape)");
+  return GS_OK;
+}
+int gs_verify_statements_rlc_dev(gs_ctx* c, int ty, size_t S, size_t E, int m, int n, const void* A, const void* B,
+                                 const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                                 const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
+  RC(check_stmt_rlc(c, ty, S, E, m, n));
+  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !acc || !ok)
+    return fail(c, GS_ERR_ARG, "null pointer");
+  return DISPATCH(c, verify_stmt_rlc(c, ty, S, E, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok));
+}
+int gs_verify_statements_rlc(gs_ctx* c, int ty, size_t S, size_t E, int m, int n, const void* A, const void* B,
+                             const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                             const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
+  RC(check_stmt_rlc(c, ty, S, E, m, n));
+  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !ok) return fail(c, GS_ERR_ARG, "null pointer");
+  for (size_t i = 0; i < 4 * S * E; i++)  // a zero exponent drops its cell equation from the combined check
+    if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
+  HostStage st(c);
+  const lay::Layout L(sz_fq(c->curve), ty, E, m, n, true);
+  const void* const h[8] = {A, B, G, target, xcoms, ycoms, pi, theta};
+  static const lay::Array arr[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
+  void *d[8], *drho, *dacc, *dok;
+  std::vector<uint8_t> hacc(S * 2 * 12 * sz_fq(c->curve));
+  for (int i = 0; i < 8; i++) RC(st.in(h[i], S * L.bytes[arr[i]], &d[i]));
+  RC(st.in(rho, S * E * 4 * sizeof(uint64_t), &drho));
+  RC(st.out(hacc.data(), hacc.size(), &dacc));
+  RC(st.out(ok, S, &dok));
+  RC(gs_verify_statements_rlc_dev(c, ty, S, E, m, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], (const uint64_t*)drho,
+                                  dacc, (uint8_t*)dok));
+  RC(st.back(hacc.data(), dacc, hacc.size()));
+  RC(st.back(ok, dok, S));
+  if (acc) memcpy(acc, hacc.data(), hacc.size());
   return GS_OK;
 }
 int gs_gt_finalize_dev(gs_ctx* c, size_t count, const void* accs_dev, uint8_t* ok) {

@@ -1432,6 +1432,153 @@ template <class C> __global__ void k_gt_set_one(Fp12<C>* p) {
   p[0] = o;
 }
 
+// ---- statement-batched verifier (gs_verify_statements_rlc): the unit of every array is a STATEMENT of E equations ----
+// Fr preparation.  Output scalar o of statement s (canonical, pool of pm.total scalars per statement):
+//   [0, 4E)        RH[4e + c]                 = rho[s][e][c]
+//   then 4mn       GC[(c m + i) n + j]        = sum_e rho_e,c Gamma_e,ij
+//   then 4n  (as)  AR[4j + c]                 = sum_e rho_e,c a_ej          (scalar constants on the X side)
+//   then 4m  (bs)  BC[4i + c]                 = sum_e rho_e,c b_ei          (scalar constants on the Y side)
+//   then 4   (tq)  NR[c]                      = - sum_e rho_e,c t_e         (QuadEqu targets)
+// every sum is E products: a lane that owns ONE output never walks more than E terms.
+template <class C>
+__device__ __forceinline__ void stmt_prep_out(size_t s, int o, int E, int m, int n, const Fr<C>* G, const Fr<C>* as,
+                                              const Fr<C>* bs, const Fr<C>* tq, const uint64_t* rho, const PoolMap& pm,
+                                              Fr<C>* P) {
+  const uint64_t* rs = rho + s * (size_t)E * 4;
+  auto rho_fr = [&](int idx) {
+    Fr<C> r = fzero<FrM<C>>();
+    uint64_t v = rs[idx];
+    r.v[0] = (uint32_t)v;
+    r.v[1] = (uint32_t)(v >> 32);
+    return r;  // canonical (rho < 2^64 < r)
+  };
+  if (o < 4 * E) {
+    P[pm.RH + o] = rho_fr(o);
+    return;
+  }
+  o -= 4 * E;
+  const int mn = m * n;
+  const Fr<C>* src;
+  int stride, c, dst;
+  bool negate = false;
+  if (o < 4 * mn) {
+    c = o / mn;
+    src = G + s * (size_t)E * mn + (o % mn);
+    stride = mn;
+    dst = pm.GC + o;
+  } else {
+    o -= 4 * mn;
+    if (as && o < 4 * n) {
+      c = o & 3;
+      src = as + s * (size_t)E * n + (o >> 2);
+      stride = n;
+      dst = pm.AR + o;
+    } else {
+      if (as) o -= 4 * n;
+      if (bs && o < 4 * m) {
+        c = o & 3;
+        src = bs + s * (size_t)E * m + (o >> 2);
+        stride = m;
+        dst = pm.BC + o;
+      } else {
+        if (bs) o -= 4 * m;
+        c = o;
+        src = tq + s * (size_t)E;
+        stride = 1;
+        dst = pm.NR + o;
+        negate = true;
+      }
+    }
+  }
+  Fr<C> acc = fzero<FrM<C>>();
+  for (int e = 0; e < E; e++) acc = add(acc, mul(src[(size_t)e * stride], to_mont(rho_fr(4 * e + c))));
+  if (negate) acc = neg(acc);
+  P[dst] = from_mont(acc);
+}
+// per = 1: one lane per statement walks its nout outputs (small statements); per = nout: one lane per output scalar
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE)
+    k_prep_verify_stmt_rlc(size_t S, int E, int m, int n, int nout, int per, const Fr<C>* G, const Fr<C>* as,
+                           const Fr<C>* bs, const Fr<C>* tq, const uint64_t* rho, PoolMap pm, Fr<C>* pool) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= S * (size_t)per) return;
+  size_t s = g / per;
+  Fr<C>* P = pool + s * pm.total;
+  if (per == 1) {
+    for (int o = 0; o < nout; o++) stmt_prep_out<C>(s, o, E, m, n, G, as, bs, tq, rho, pm, P);
+  } else {
+    stmt_prep_out<C>(s, (int)(g % per), E, m, n, G, as, bs, tq, rho, pm, P);
+  }
+}
+
+// segmented product: S segments of len_in elements each -> S segments of len_out = ceil(len_in / K) products of runs
+// of K (the host repeats it until len_out = 1, as gt_product does for one segment)
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE) k_gt_prod_seg(size_t S, size_t len_in, const Fp12<C>* in, size_t len_out,
+                                                            Fp12<C>* out, int K) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= S * len_out) return;
+  size_t s = g / len_out, r = g % len_out;
+  size_t lo = r * (size_t)K, hi = lo + K < len_in ? lo + K : len_in;
+  const Fp12<C>* p = in + s * len_in;
+  Fp12<C> acc = p[lo];
+  for (size_t i = lo + 1; i < hi; i++) f12_mul(acc, acc, p[i]);
+  out[s * len_out + r] = acc;
+}
+
+// One statement: product of its ntask Miller partials (the un-exponentiated accumulator), final exponentiation,
+// comparison with the statement's target product (tprod; null = one).  Writes the verdict and the boundary-form pair
+// (acc[s][0] = Miller product, acc[s][1] = target product) that gs_gt_finalize takes.
+template <class C>
+__device__ __forceinline__ void stmt_product(Fp12<C>& f, Fp12<C>& t, const Fp12<C>* mpart, const Fp12<C>* tprod, size_t s,
+                                             int ntask) {
+  const Fp12<C>* p = mpart + s * (size_t)ntask;
+  f = p[0];
+  for (int i = 1; i < ntask; i++) f12_mul(f, f, p[i]);
+  if (tprod)
+    t = tprod[s];
+  else
+    f12_one(t);
+}
+template <class C>
+struct k_stmt_final {
+  static __device__ __forceinline__ void run(size_t s, size_t S, int ntask, const Fp12<C>* mpart, const Fp12<C>* tprod,
+                                             uint8_t* acc, uint8_t* ok) {
+  if (s >= S) return;
+  Fp12<C> f, t, r;
+  stmt_product(f, t, mpart, tprod, s, ntask);
+  BFq<C>* a = reinterpret_cast<BFq<C>*>(acc) + 24 * s;
+  f12_to_boundary<C>(a, f);
+  f12_to_boundary<C>(a + 12, t);
+  final_exp(r, f);
+  ok[s] = f12_eq(r, t) ? 1 : 0;
+}
+};
+// The same with a 3-lane group per statement (gs_coop.cuh; blockDim.x == 63: 21 groups per wave, idle groups of the
+// last wave shadow the last statement so that every lane reaches the shuffles)
+template <class C>
+struct k_stmt_final_coop {
+  static __device__ __forceinline__ void run(size_t gt, size_t S, int ntask, const Fp12<C>* mpart, const Fp12<C>* tprod,
+                                             uint8_t* acc, uint8_t* ok) {
+  int lane = (int)(gt % 63), j = lane % 3;
+  size_t s = (gt / 63) * 21 + lane / 3;
+  bool live = s < S;
+  if (!live) s = S - 1;
+  Fp12<C> f, t, r;
+  stmt_product(f, t, mpart, tprod, s, ntask);
+  if (live && j == 0) {
+    BFq<C>* a = reinterpret_cast<BFq<C>*>(acc) + 24 * s;
+    f12_to_boundary<C>(a, f);
+    f12_to_boundary<C>(a + 12, t);
+  }
+  CoopWave xw{lane - j};
+  ExpXCoop<C, CoopWave> ex{j, &xw};
+  final_exp_with(r, f, ex);
+  bool same = f12_eq(r, t);
+  if (live && j == 0) ok[s] = same ? 1 : 0;
+}
+};
+
 // --------------------------------------------------------------------------
 // wire format (gs_wire.cuh): arrays of elements, one lane per element
 // --------------------------------------------------------------------------

@@ -332,6 +332,19 @@ class QuadEqu(_Equation):
     TYPE = GS_QUAD
 
 
+def _draw_rho(rng, count):
+    """`count` non-zero 64-bit exponents for the batched verifiers from the caller's CSPRNG (the rho contract of
+    gs_amd.h: fresh per call, secret until the verdict, drawn after the proofs are fixed).  Uses rng.u64() when the
+    generator has one, else the low limb of a uniform scalar rng.fr(); a zero is drawn again."""
+    out = np.zeros(count, dtype=np.uint64)
+    for i in range(count):
+        v = 0
+        while v == 0:
+            v = int(rng.u64()) if hasattr(rng, "u64") else int(np.asarray(rng.fr(), dtype=np.uint64).reshape(-1)[0])
+        out[i] = v
+    return out
+
+
 class Statement:
     """`pub type Statement = Vec<dyn Equ>` (statement.rs:109) made usable: a list of equations of ONE type over the same
     variables (statement.rs:24-28: "each equation is defined with respect to the list of variables that span across
@@ -370,6 +383,12 @@ class Statement:
 
     def verify(self, com_proof, crs):
         """[bool per equation]; the statement holds iff all are true"""
+        m, n, arrays = self._arrays(com_proof)
+        ok = crs.engine.verify_statement(self.TYPE, len(self.equations), m, n, *arrays)
+        return [bool(v) for v in ok]
+
+    def _arrays(self, com_proof):
+        """(m, n, the eight arrays of gs_verify_statement) after the length checks of verify()"""
         kx, ky = self._kxky()
         E = len(self.equations)
         assert len(com_proof.equ_proofs) == E
@@ -379,13 +398,21 @@ class Statement:
             equ._check_statement_shape(m, n)
             assert pf.equ_type == self.TYPE and len(pf.pi) == kx and len(pf.theta) == ky
         cat = np.concatenate
-        ok = crs.engine.verify_statement(
-            self.TYPE, E, m, n, cat([_cat(e.a_consts, 0) for e in self.equations]),
+        return m, n, (
+            cat([_cat(e.a_consts, 0) for e in self.equations]),
             cat([_cat(e.b_consts, 0) for e in self.equations]), cat([_flat_mat(e.gamma) for e in self.equations]),
             cat([np.asarray(e.target, dtype=np.uint64).reshape(-1) for e in self.equations]),
             _cat(com_proof.xcoms.coms, 0), _cat(com_proof.ycoms.coms, 0),
             cat([_cat(pf.pi, 0) for pf in com_proof.equ_proofs]), cat([_cat(pf.theta, 0) for pf in com_proof.equ_proofs]))
-        return [bool(v) for v in ok]
+
+    def verify_rlc(self, com_proof, crs, rng):
+        """ONE verdict for the whole statement from one combined pairing check (gs_verify_statements_rlc, S = 1): the
+        pairing work does not grow with the number of equations.  Accepts what verify() accepts on every equation;
+        a statement with a false equation passes with probability 2^-64 over rho, which is drawn here from `rng`."""
+        m, n, arrays = self._arrays(com_proof)
+        E = len(self.equations)
+        ok, _ = crs.engine.verify_statements_rlc(self.TYPE, 1, E, m, n, *arrays, _draw_rho(rng, 4 * E))
+        return bool(ok[0])
 
 
 class MixedProof:
@@ -453,6 +480,26 @@ class MixedStatement:
 
     def verify(self, proof, crs):
         """[bool per equation], in the order of the statement's equations"""
+        oks = crs.engine.verify_mixed(self._verify_parts(proof))
+        out = [None] * len(self.equations)
+        for (ty, idx), ok in zip(self._by_type(), oks):
+            for k, i in enumerate(idx):
+                out[i] = bool(ok[k])
+        return out
+
+    def verify_rlc(self, proof, crs, rng):
+        """ONE verdict for the whole mixed statement: one combined check per equation type
+        (gs_verify_statements_rlc, S = 1) and one gs_gt_finalize over the types' accumulator pairs."""
+        pairs = []
+        for p in self._verify_parts(proof):
+            _, acc = crs.engine.verify_statements_rlc(p["ty"], 1, p["N"], p["m"], p["n"], p["A"], p["B"], p["Gamma"],
+                                                      p["target"], p["xcoms"], p["ycoms"], p["pi"], p["theta"],
+                                                      _draw_rho(rng, 4 * p["N"]))
+            pairs.append(acc.reshape(-1))
+        return bool(crs.engine.gt_finalize(np.concatenate(pairs)))
+
+    def _verify_parts(self, proof):
+        """one shared-variables part per equation type, in the order of _by_type()"""
         coms = dict(xg=proof.com_xg, yg=proof.com_yg, xs=proof.com_xs, ys=proof.com_ys)
         assert len(proof.equ_proofs) == len(self.equations)
         cat = np.concatenate
@@ -472,9 +519,4 @@ class MixedStatement:
                               target=cat([np.asarray(e.target, dtype=np.uint64).reshape(-1) for e in eqs]),
                               xcoms=_cat(coms[gx].coms, 0), ycoms=_cat(coms[gy].coms, 0),
                               pi=cat([_cat(pf.pi, 0) for pf in pfs]), theta=cat([_cat(pf.theta, 0) for pf in pfs])))
-        oks = crs.engine.verify_mixed(parts)
-        out = [None] * len(self.equations)
-        for (ty, idx), ok in zip(self._by_type(), oks):
-            for k, i in enumerate(idx):
-                out[i] = bool(ok[k])
-        return out
+        return parts

@@ -401,6 +401,29 @@ int gs_verify_batch_rlc_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const
 int gs_verify_batch_rlc(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
                         const void* Gamma, const void* target, const void* xcoms, const void* ycoms, const void* pi,
                         const void* theta, const uint64_t* rho, void* acc_gt, uint8_t* ok_all);
+/* Batched verifier for STATEMENTS: S statements of one type and shape, each E equations over ONE set of commitments
+ * (the arrays of statement s are exactly what gs_verify_statement takes, at offset s: A[S][E][n], B[S][E][m],
+ * Gamma[S][E][m][n], target[S][E], xcoms[S][m], ycoms[S][n], pi[S][E][kx], theta[S][E][ky]; rho[S][E][4] u64).
+ * The random linear combination is taken ACROSS the equations of a statement before anything is paired, so a
+ * statement costs 2n + 2m + 2kx + 2ky Miller pairs (fewer with scalar constants) whatever E is; the E-dependent work
+ * is short-scalar sums in G1 / G2.  One verdict per statement: ok[S].
+ * acc_gt[S][2] (may be NULL for the host entry) receives one accumulator pair per statement in the convention of
+ * gs_verify_batch_rlc: acc[s][0] = the un-exponentiated Miller product, FE(acc[s][0]) = prod_e prod_cells
+ * (lhs / rhs without the PPE target)^rho_e,cell; acc[s][1] = prod_e t_e^rho_e,11 for PPE, one otherwise;
+ * ok[s] = (FE(acc[s][0]) == acc[s][1]).
+ * RHO CONTRACT (soundness rests on it), as for gs_verify_batch_rlc: every rho is drawn from a CSPRNG, fresh for every
+ * call, NON-ZERO, secret until the verdict is out, and drawn AFTER the commitments and proofs are fixed; the soundness
+ * error is 2^-64 per statement.  The host entry rejects rho == 0 (GS_ERR_ARG); the _dev entry cannot look.  PPE targets
+ * are raised to rho WITHOUT a subgroup check.
+ * A statement that mixes equation types is checked with one call per type (S = 1) and the pairs handed to
+ * gs_gt_finalize: the verdict of the whole statement.  S = 0 or E = 0 is GS_ERR_ARG; a statement whose arrays the
+ * plan cannot index (32-bit byte strides per statement) is GS_ERR_SHAPE. */
+int gs_verify_statements_rlc_dev(gs_ctx*, int equ_type, size_t S, size_t E, int m, int n, const void* A, const void* B,
+                                 const void* Gamma, const void* target, const void* xcoms, const void* ycoms,
+                                 const void* pi, const void* theta, const uint64_t* rho, void* acc_gt, uint8_t* ok);
+int gs_verify_statements_rlc(gs_ctx*, int equ_type, size_t S, size_t E, int m, int n, const void* A, const void* B,
+                             const void* Gamma, const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                             const void* theta, const uint64_t* rho, void* acc_gt, uint8_t* ok);
 /* product of `count` GT accumulator pairs (host), final exponentiation, FE(prod acc[0]) == prod acc[1] ? */
 int gs_gt_finalize(gs_ctx*, size_t count, const void* accs_gt_host, uint8_t* ok_all);
 /* the same with the pairs in this context's device memory (e.g. the receive buffer of an all-gather); ok_all on the host */

@@ -325,6 +325,15 @@ inline Matrix<Fr> fr_matmul(const Ctx& cx, const Matrix<Fr>& a, const Matrix<Fr>
     for (size_t j = 0; j < cols; j++) out[i].push_back(Fr{Bytes(o.begin() + (i * cols + j) * 32, o.begin() + (i * cols + j + 1) * 32)});
   return out;
 }
+// one 64-bit draw for the batched verifiers' exponents: rng.u64() when the generator has one, else the low limb of a
+// uniform scalar rng.fr() (as mirror._draw_rho does)
+template <class Rng> auto draw_u64(Rng& rng, int) -> decltype((uint64_t)rng.u64()) { return (uint64_t)rng.u64(); }
+template <class Rng> uint64_t draw_u64(Rng& rng, long) {
+  Fr f = rng.fr();
+  uint64_t r = 0;
+  std::memcpy(&r, f.v.data(), sizeof r);
+  return r;
+}
 }  // namespace detail
 
 // commit.rs:78-100, 178-200, 125-156, 225-256 (+ the single-element forms :59-75, 103-122, 159-175, 203-222)
@@ -636,14 +645,22 @@ class Statement {
     return out;
   }
 
-  // one verdict per equation, in the statement's order; the statement holds iff all are true
-  std::vector<bool> verify(const StatementProof& pr, const CRS& crs) const {
+ private:
+  // the verifier's arrays of every part (one per equation type, shared commitments), after the length checks
+  struct VerifyArrays {
+    std::vector<Part> ps;
+    Bytes Cxg, Cyg, Cxs, Cys;
+    std::vector<gs_verify_part> cp;
+  };
+  void verify_arrays(const StatementProof& pr, const Ctx& cx, VerifyArrays& va) const {
     assert_eq(pr.equ_proofs.size(), items.size(), "proof.equ_proofs.len() == statement.len()");
-    const Ctx& cx = *crs.ctx;
-    std::vector<Part> ps = parts();
+    va.ps = parts();
+    std::vector<Part>& ps = va.ps;
     if (ps.size() > GS_MIXED_MAX) throw Panic("more equation types than a mixed call takes");
-    std::vector<gs_verify_part> cp(ps.size());
-    Bytes Cxg = cat(pr.com_xg.coms), Cyg = cat(pr.com_yg.coms), Cxs = cat(pr.com_xs.coms), Cys = cat(pr.com_ys.coms);
+    va.cp.resize(ps.size());
+    std::vector<gs_verify_part>& cp = va.cp;
+    va.Cxg = cat(pr.com_xg.coms), va.Cyg = cat(pr.com_yg.coms), va.Cxs = cat(pr.com_xs.coms), va.Cys = cat(pr.com_ys.coms);
+    const Bytes &Cxg = va.Cxg, &Cyg = va.Cyg, &Cxs = va.Cxs, &Cys = va.Cys;
     for (size_t k = 0; k < ps.size(); k++) {
       Part& p = ps[k];
       const bool xg = xgroup(p.ty), yg = ygroup(p.ty);
@@ -679,11 +696,46 @@ class Statement {
       cp[k] = gs_verify_part{(int)p.ty, E, (int)m, (int)n, p.A.data(), p.B.data(), p.G.data(), p.target.data(),
                              (xg ? Cxg : Cxs).data(), (yg ? Cyg : Cys).data(), p.pi.data(), p.theta.data(), p.ok.data(), 1};
     }
-    cx.chk(gs_verify_mixed(cx.c, (int)cp.size(), cp.data()));
+  }
+
+ public:
+  // one verdict per equation, in the statement's order; the statement holds iff all are true
+  std::vector<bool> verify(const StatementProof& pr, const CRS& crs) const {
+    const Ctx& cx = *crs.ctx;
+    VerifyArrays va;
+    verify_arrays(pr, cx, va);
+    cx.chk(gs_verify_mixed(cx.c, (int)va.cp.size(), va.cp.data()));
     std::vector<bool> out(items.size(), false);
-    for (const Part& p : ps)
+    for (const Part& p : va.ps)
       for (size_t e = 0; e < p.idx.size(); e++) out[p.idx[e]] = p.ok[e] != 0;
     return out;
+  }
+
+  // ONE verdict for the whole statement from one combined pairing check per equation type (gs_verify_statements_rlc
+  // with S = 1: the pairing work does not grow with the number of equations) and one gs_gt_finalize over the types'
+  // accumulator pairs.  Accepts what verify() accepts on every equation; a statement with a false equation passes
+  // with probability 2^-64 over rho, drawn here from `rng` (rng.u64() when it has one, else the low 64 bits of rng.fr(); non-zero) -- the rho
+  // contract of gs_amd.h: a CSPRNG, fresh per call, drawn after the proof is fixed.
+  template <class Rng> bool verify_rlc(const StatementProof& pr, const CRS& crs, Rng& rng) const {
+    const Ctx& cx = *crs.ctx;
+    VerifyArrays va;
+    verify_arrays(pr, cx, va);
+    Bytes pairs;
+    for (const gs_verify_part& p : va.cp) {
+      std::vector<uint64_t> rho(4 * p.N);
+      for (uint64_t& r : rho)
+        while (r == 0) {
+          r = detail::draw_u64(rng, 0);
+        }
+      Bytes acc(2 * cx.sz[4]);
+      uint8_t ok = 0;
+      cx.chk(gs_verify_statements_rlc(cx.c, p.equ_type, 1, p.N, p.m, p.n, p.A, p.B, p.Gamma, p.target, p.xcoms, p.ycoms,
+                                      p.pi, p.theta, rho.data(), acc.data(), &ok));
+      pairs.insert(pairs.end(), acc.begin(), acc.end());
+    }
+    uint8_t all = 0;
+    cx.chk(gs_gt_finalize(cx.c, va.cp.size(), pairs.data(), &all));
+    return all != 0;
   }
 };
 
