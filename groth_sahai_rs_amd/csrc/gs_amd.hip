@@ -696,6 +696,30 @@ static std::vector<double> miller_budgets(const gs_ctx* c, bool twin) {
     }
   return out;
 }
+// single-accumulator task list over the pairs `pr` of an equation: the budget of least planned cost
+static std::vector<MillerTask> plan_miller_single(const gs_ctx* c, size_t N, const std::vector<PairRef>& pr) {
+  std::vector<MillerTask> mt;
+  double best = -1;
+  for (double cand : miller_budgets(c, false)) {
+    std::vector<MillerTask> tmp;
+    chunk_tasks(tmp, pr, cand, 0, true, mcost(c->curve, false), c->line_tables);
+    double cost = miller_cost(c, N, tmp, false);
+    if (best < 0 || cost < best) {
+      best = cost;
+      mt = tmp;
+    }
+  }
+  return mt;
+}
+// work of a Miller launch: (P, Q) pairs (twin: (Q, P0, P1) triples) per equation, a table-reading pair counted at its
+// cost ratio
+static void miller_work_hint(gs_ctx* c, size_t N, const std::vector<MillerTask>& mt, bool twin) {
+  const MCost mc = mcost(c->curve, twin);
+  double pairs = 0;
+  for (const MillerTask& t : mt)
+    for (int q = 0; q < t.np; q++) pairs += pair_fixed(c->line_tables, t.pr[q]) ? mc.fix / mc.var : 1.0;
+  c->work_hint = (uint64_t)((double)N * pairs);
+}
 
 // k_var_multi lanes per launch: their Straus tables (affine table + the Jacobian staging of its build) live in a
 // per-context workspace of 9 .. 70 KB per lane (G2, 8 terms, 5-bit windows: 28 + 42 KB).  Two rounds of resident waves
@@ -928,6 +952,7 @@ template <class T> static int upload(gs_ctx* c, const char* name, const std::vec
     }
     for (; i < nb; i++) h = (h ^ b[i]) * 1099511628211ull;
   }
+  if (getenv("GS_PLAN_TRACE")) fprintf(stderr, "[plan] table %s %zu %016llx\n", name, v.size(), (unsigned long long)h);
   for (int salt = 0;; salt++) {
     char key[176];
     snprintf(key, sizeof key, "plan%s.%zu.%016llx.%d", name, v.size(), (unsigned long long)h, salt);
@@ -1013,6 +1038,43 @@ static RedTask mkred(int b0, int e0, int b1, int e1, int out_arr, int out_idx) {
   r.pad = r.pad1 = r.pad2 = 0;
   return r;
 }
+static void add_pair(std::vector<PairRef>& v, int p_arr, int p_idx, int neg, int q_arr, int q_idx) {
+  PairRef r;
+  r.p_arr = (uint8_t)p_arr;
+  r.p_idx = (uint32_t)p_idx;
+  r.neg = (uint8_t)neg;
+  r.q_arr = (uint8_t)q_arr;
+  r.q_idx = (uint32_t)q_idx;
+  r.pad = 0;
+  v.push_back(r);
+}
+// An array table in one expression: arr_tab({{i, base, bytes per equation[, present]}, ...}).  Entries that are not
+// named, or not present, stay zero.
+struct ArrEnt {
+  int i;
+  const void* base;
+  uint32_t stride;
+  bool present = true;
+};
+static ArrTab arr_tab(std::initializer_list<ArrEnt> ents) {
+  ArrTab t;
+  memset(&t, 0, sizeof t);
+  for (const ArrEnt& e : ents)
+    if (e.present) {
+      t.base[e.i] = (const uint8_t*)e.base;
+      t.stride[e.i] = e.stride;
+    }
+  return t;
+}
+static OutTab out_tab(void* base0, uint32_t stride0, void* base1 = nullptr, uint32_t stride1 = 0) {
+  OutTab t;
+  memset(&t, 0, sizeof t);
+  t.base[0] = (uint8_t*)base0;
+  t.stride[0] = stride0;
+  t.base[1] = (uint8_t*)base1;
+  t.stride[1] = stride1;
+  return t;
+}
 
 // Append the variable-base terms of ONE output point: chunks of <= tm terms share a lane
 // (and one partial slot); with tm == 1 every term is its own lane/slot.
@@ -1038,6 +1100,32 @@ static void add_var_terms(SidePlan& sp, const std::vector<VarTask>& terms, int& 
     slot++;
   }
 }
+// Plans Com-shaped outputs (two components each).  The components of an output occupy consecutive runs of partial
+// slots, in the order in which `emit(q, comp, out)` asks for them: out.fix(...) takes one slot for a fixed-base task
+// (mkfix without its slot), out.terms(list) as many as add_var_terms gives the list.  A reduction over the two runs
+// closes every output.
+struct ComOutputs {
+  SidePlan& sp;
+  int slot = 0;
+  void fix(int s0, int t0, int s1, int t1, int a_arr, int a_idx, int a_neg = 0) {
+    sp.fix.push_back(mkfix(s0, t0, s1, t1, a_arr, a_idx, slot, a_neg));
+    slot++;
+  }
+  void terms(const std::vector<VarTask>& t) { add_var_terms(sp, t, slot); }
+  // outputs out0 .. out0 + count - 1 of array out_arr; emit's q runs from 0
+  template <class Emit> void add(int count, int out_arr, int out0, Emit emit) {
+    for (int q = 0; q < count; q++) {
+      int b[2], e[2];
+      for (int comp = 0; comp < 2; comp++) {
+        b[comp] = slot;
+        emit(q, comp, *this);
+        e[comp] = slot;
+      }
+      sp.red.push_back(mkred(b[0], e[0], b[1], e[1], out_arr, out0 + q));
+    }
+    sp.nslots = slot;
+  }
+};
 // Lane cost of the joint MSM in Fq multiplications: one table build of `nt` bases (2^(w-1) entries each: doublings,
 // mixed additions, 7 multiplications per entry for the common denominator) + `no` main loops (w doublings per window,
 // one mixed addition per non-zero digit, the endomorphism on the looked-up entry).
@@ -1048,10 +1136,6 @@ static double straus_lane_cost(bool g2, bool bn, int nt, int no, int w) {
   double run = (nd - 1) * w * dbl + (double)nt * ns * (nd - 0.5) * (1.0 - 1.0 / (2 * ne)) * (madd + endo);
   return build + no * run;
 }
-// Variable-base terms per lane (joint Straus MSM, shared doubling chain) for a side with `T` terms per output
-// and `outputs` outputs per equation.  Same cost model as miller_cost: rounds of waves x lane length, lane(nt) =
-// D + P nt Fq multiplications (fits of profiles/r1/fq_mul_counts.json, the same within 3 % on both curves now that
-// both have endomorphism decompositions: G1 832 + 829 nt, G2 1000 + 2365 nt).
 // Lane-time multiplier of a launch of `waves` waves.  The Fp2 / Fp12 kernels and the BLS12-381 G1 kernels hold one
 // wave per SIMD: whole rounds while there are few.  The BN254 G1 Straus kernels come out of the compiler at 252
 // registers and run two waves per SIMD; two resident waves finish in 2 / 1.55 of the time of one (measured at 2^16:
@@ -1065,6 +1149,10 @@ static double wave_rounds(const gs_ctx* c, double waves, bool g2) {
   const double gain = 1.55;
   return r <= gain ? 1.0 : r / gain;
 }
+// Variable-base terms per lane (joint Straus MSM, shared doubling chain) for a side with `T` terms per output
+// and `outputs` outputs per equation.  Same cost model as miller_cost: rounds of waves x lane length, lane(nt) =
+// D + P nt Fq multiplications (fits of profiles/r1/fq_mul_counts.json, the same within 3 % on both curves now that
+// both have endomorphism decompositions: G1 832 + 829 nt, G2 1000 + 2365 nt).
 static int pick_tm(const gs_ctx* c, size_t N, int T, int outputs, bool g2, int share) {
   // `share` of the `outputs` run over the same bases (share_tables() can give them one table build per lane): the
   // group size is chosen together with the outputs per lane and the window width that share_tables() will then pick
@@ -1204,39 +1292,25 @@ static void share_tables(const gs_ctx* c, size_t N, SidePlan& sp, bool g2) {
 //  arrays: 0 = variables (group), 1 = constants (group)
 static void build_side(SidePlan& sp, bool want_coms, int nv, int nc, bool group, int kc, int npf, int rc, int vc,
                        int cs, int ph, int f0, int sg) {
-  int slot = 0;
+  ComOutputs out{sp};
   if (want_coms) {
-    for (int i = 0; i < nv; i++) {
-      int s_begin = slot;
-      for (int c = 0; c < 2; c++) {
-        if (group)
-          sp.fix.push_back(mkfix(rc + 2 * i, tb_u(0, c), rc + 2 * i + 1, tb_u(1, c), c ? 0 : 0xFF, i, slot++));
-        else
-          sp.fix.push_back(mkfix(vc + i, tb_w(c), rc + i, tb_u(0, c), 0xFF, 0, slot++));
-      }
-      sp.red.push_back(mkred(s_begin, s_begin + 1, s_begin + 1, s_begin + 2, 0, i));
-    }
+    out.add(nv, 0, 0, [&](int i, int c, ComOutputs& o) {
+      if (group)
+        o.fix(rc + 2 * i, tb_u(0, c), rc + 2 * i + 1, tb_u(1, c), c ? 0 : 0xFF, i);
+      else
+        o.fix(vc + i, tb_w(c), rc + i, tb_u(0, c), 0xFF, 0);
+    });
     sp.ncom = nv;
   }
-  for (int l = 0; l < npf; l++) {
-    int b0 = slot;
-    if (group) {
-      sp.fix.push_back(mkfix(f0 + l * 2, tb_u(0, 0), f0 + l * 2 + 1, tb_u(1, 0), 0xFF, 0, slot++));
-      int b1 = slot;
-      sp.fix.push_back(mkfix(f0 + l * 2, tb_u(0, 1), f0 + l * 2 + 1, tb_u(1, 1), 0xFF, 0, slot++));
-      std::vector<VarTask> terms;
-      for (int j = 0; j < nc; j++) terms.push_back(mkvar(cs + j * npf + l, 1, j, 0));
-      for (int i = 0; i < nv; i++) terms.push_back(mkvar(ph + l * nv + i, 0, i, 0));
-      add_var_terms(sp, terms, slot);
-      sp.red.push_back(mkred(b0, b1, b1, slot, 1, l));
-    } else {
-      sp.fix.push_back(mkfix(sg + l, tb_w(0), f0 + l, tb_u(0, 0), 0xFF, 0, slot++));
-      int b1 = slot;
-      sp.fix.push_back(mkfix(sg + l, tb_w(1), f0 + l, tb_u(0, 1), 0xFF, 0, slot++));
-      sp.red.push_back(mkred(b0, b1, b1, slot, 1, l));
-    }
-  }
-  sp.nslots = slot;
+  out.add(npf, 1, 0, [&](int l, int c, ComOutputs& o) {
+    if (!group) return o.fix(sg + l, tb_w(c), f0 + l, tb_u(0, c), 0xFF, 0);
+    o.fix(f0 + l * 2, tb_u(0, c), f0 + l * 2 + 1, tb_u(1, c), 0xFF, 0);
+    if (c == 0) return;  // iota(const) = (O, const), and the variables enter through component 1 alone
+    std::vector<VarTask> terms;
+    for (int j = 0; j < nc; j++) terms.push_back(mkvar(cs + j * npf + l, 1, j, 0));
+    for (int i = 0; i < nv; i++) terms.push_back(mkvar(ph + l * nv + i, 0, i, 0));
+    o.terms(terms);
+  });
 }
 
 // Build the plan of one side of a RERANDOMIZATION (no witness: the variables are known only through their old
@@ -1250,38 +1324,27 @@ static void build_side(SidePlan& sp, bool want_coms, int nv, int nc, bool group,
 //    pf'_l.c    = pf_l.c + f0_l . key.c [+ sg_l W.c] + sum_i ph_li com_i.c [+ (c = 1) sum_j cs_jl const_j]
 static void build_rerand_side(SidePlan& sp, bool want_coms, int nv, int nc, bool group, int kc, int npf, int rc, int cs,
                               int ph, int f0, int sg) {
-  int slot = 0;
+  ComOutputs out{sp};
   if (want_coms) {
-    for (int i = 0; i < nv; i++) {
-      int s_begin = slot;
-      for (int c = 0; c < 2; c++) {
-        if (group)
-          sp.fix.push_back(mkfix(rc + 2 * i, tb_u(0, c), rc + 2 * i + 1, tb_u(1, c), 0, 2 * i + c, slot++));
-        else
-          sp.fix.push_back(mkfix(rc + i, tb_u(0, c), 0, 0xFF, 0, 2 * i + c, slot++));
-      }
-      sp.red.push_back(mkred(s_begin, s_begin + 1, s_begin + 1, s_begin + 2, 0, i));
-    }
+    out.add(nv, 0, 0, [&](int i, int c, ComOutputs& o) {
+      if (group)
+        o.fix(rc + 2 * i, tb_u(0, c), rc + 2 * i + 1, tb_u(1, c), 0, 2 * i + c);
+      else
+        o.fix(rc + i, tb_u(0, c), 0, 0xFF, 0, 2 * i + c);
+    });
     sp.ncom = nv;
   }
-  for (int l = 0; l < npf; l++) {
-    int b[2], e[2];
-    for (int c = 0; c < 2; c++) {
-      b[c] = slot;
-      if (group)
-        sp.fix.push_back(mkfix(f0 + l * 2, tb_u(0, c), f0 + l * 2 + 1, tb_u(1, c), 2, 2 * l + c, slot++));
-      else
-        sp.fix.push_back(mkfix(sg + l, tb_w(c), f0 + l, tb_u(0, c), 2, 2 * l + c, slot++));
-      std::vector<VarTask> terms;
-      if (group && c == 1)  // iota(const) = (O, const)
-        for (int j = 0; j < nc; j++) terms.push_back(mkvar(cs + j * npf + l, 1, j, 0));
-      for (int i = 0; i < nv; i++) terms.push_back(mkvar(ph + l * nv + i, 0, 2 * i + c, 0));
-      add_var_terms(sp, terms, slot);
-      e[c] = slot;
-    }
-    sp.red.push_back(mkred(b[0], e[0], b[1], e[1], 1, l));
-  }
-  sp.nslots = slot;
+  out.add(npf, 1, 0, [&](int l, int c, ComOutputs& o) {
+    if (group)
+      o.fix(f0 + l * 2, tb_u(0, c), f0 + l * 2 + 1, tb_u(1, c), 2, 2 * l + c);
+    else
+      o.fix(sg + l, tb_w(c), f0 + l, tb_u(0, c), 2, 2 * l + c);
+    std::vector<VarTask> terms;
+    if (group && c == 1)  // iota(const) = (O, const)
+      for (int j = 0; j < nc; j++) terms.push_back(mkvar(cs + j * npf + l, 1, j, 0));
+    for (int i = 0; i < nv; i++) terms.push_back(mkvar(ph + l * nv + i, 0, 2 * i + c, 0));
+    o.terms(terms);
+  });
 }
 
 // the reduction launch of a side, kept back so that the caller can run the two sides' reductions side by side
@@ -1601,6 +1664,26 @@ template <class C> struct Impl {
     return pm;
   }
 
+  // The prover's scalar preparation into `pool`, launched as `name` (large arities: `name`.a and .b, one lane per
+  // output scalar).  xs / ys: scalar witnesses, as / bs: scalar constants; null where that side is group-valued or
+  // (rerandomization) there is no witness.
+  static int prep_prove(gs_ctx* c, const std::string& name, size_t N, int m, int n, int kx, int ky, const void* G,
+                        const void* R, const void* Sm, const void* T, const void* xs, const void* ys, const void* as,
+                        const void* bs, const PoolMap& pm, void* pool, bool shared) {
+    if (wide_prep(m, n)) {
+      int W = m * kx + n * ky + ky * kx + m + n + kx * n + ky * m;
+      RC(launch_seg<k_prep_prove_wide_a<C>>(c, (name + ".a").c_str(), N * (size_t)W, 64, N * (size_t)W, W, m, n, kx, ky,
+                (const S*)G, (const S*)R, (const S*)Sm, (const S*)T, (const S*)xs, (const S*)ys, pm, (S*)pool,
+                shared ? 1 : 0));
+      size_t tb = N * (size_t)(kx * ky + kx + ky);
+      return launch_seg<k_prep_prove_wide_b<C>>(c, (name + ".b").c_str(), tb, 64, tb, m, n, kx, ky, (const S*)R,
+                (const S*)Sm, (const S*)T, (const S*)xs, (const S*)ys, (const S*)as, (const S*)bs, pm, (S*)pool,
+                shared ? 1 : 0);
+    }
+    return launch_seg<k_prep_prove<C>>(c, name.c_str(), N, 64, N, m, n, kx, ky, (const S*)G, (const S*)R, (const S*)Sm,
+              (const S*)T, (const S*)xs, (const S*)ys, (const S*)as, (const S*)bs, pm, (S*)pool, shared ? 1 : 0);
+  }
+
   // prove / commit_and_prove for all four types (prove.rs:71-489)
   // shared: a Statement -- the N equations are over the SAME variables X, Y and commit randomness R, S (one copy,
   // stride 0); constants, Gamma, T and the proofs stay per equation.  Commitments are then made once by the caller.
@@ -1616,20 +1699,8 @@ template <class C> struct Impl {
     // (host-pointer calls: the scalars first; group-valued variables and constants are not read before their side)
     RC(need(c, BIT(PI_G) | BIT(PI_R) | BIT(PI_S) | BIT(PI_T) | (xg ? 0u : BIT(PI_X) | BIT(PI_A)) |
                    (yg ? 0u : BIT(PI_Y) | BIT(PI_B))));
-    if (wide_prep(m, n)) {  // large arity: one lane per output scalar
-      int W = m * kx + n * ky + ky * kx + m + n + kx * n + ky * m;
-      RC(launch_seg<k_prep_prove_wide_a<C>>(c, "k_prep_prove.a", N * (size_t)W, 64, N * (size_t)W, W, m, n, kx, ky,
-                (const S*)G, (const S*)R, (const S*)Sm, (const S*)T, xg ? nullptr : (const S*)X,
-                yg ? nullptr : (const S*)Y, pm, (S*)pool, shared ? 1 : 0));
-      size_t tb = N * (size_t)(kx * ky + kx + ky);
-      RC(launch_seg<k_prep_prove_wide_b<C>>(c, "k_prep_prove.b", tb, 64, tb, m, n, kx, ky, (const S*)R, (const S*)Sm,
-                (const S*)T, xg ? nullptr : (const S*)X, yg ? nullptr : (const S*)Y, xg ? nullptr : (const S*)A,
-                yg ? nullptr : (const S*)B, pm, (S*)pool, shared ? 1 : 0));
-    } else {
-      RC(launch_seg<k_prep_prove<C>>(c, "k_prep_prove", N, 64, N, m, n, kx, ky, (const S*)G, (const S*)R, (const S*)Sm,
-                (const S*)T, xg ? nullptr : (const S*)X, yg ? nullptr : (const S*)Y, xg ? nullptr : (const S*)A,
-                yg ? nullptr : (const S*)B, pm, (S*)pool, shared ? 1 : 0));
-    }
+    RC(prep_prove(c, "k_prep_prove", N, m, n, kx, ky, G, R, Sm, T, xg ? nullptr : X, yg ? nullptr : Y, xg ? nullptr : A,
+                  yg ? nullptr : B, pm, pool, shared));
     // small batches: G1 side on the context's stream, G2 side on side[0], each side's variable-base kernel on a
     // further stream; everything joins back before this function returns
     struct CurGuard {
@@ -1646,56 +1717,34 @@ template <class C> struct Impl {
     // (larger batches once ran the two sides' reduction kernels side by side on a second stream: +1-2 % at 2^12..2^16,
     // but the extra queue's scratch reservation cost later big kernels 4x -- profiles/r3/scratch_pool.txt.  Removed.)
     // G1 side: xcoms (m) + theta (ky).  constants A (len n) multiply S; Phi multiplies X; fixed part T.
-    auto side_g1 = [&]() -> int {
-      SidePlan sp;
-      sp.tm = xg ? pick_tm(c, fillN(c, N), m + n, ky, false, ky) : 1;
-      build_side(sp, xcoms != nullptr, m, n, xg, kx, ky, pm.RC, pm.XC, pm.SC, pm.PHI, pm.TC, pm.SIG);
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      if (xg) {
-        arrs.base[0] = (const uint8_t*)X;
-        arrs.stride[0] = shared ? 0u : (uint32_t)(m * Z::G1);
-        arrs.base[1] = (const uint8_t*)A;
-        arrs.stride[1] = (uint32_t)(n * Z::G1);
-      }
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)xcoms;
-      outs.stride[0] = (uint32_t)(m * Z::COM1);
-      outs.base[1] = (uint8_t*)theta;
-      outs.stride[1] = (uint32_t)(ky * Z::COM1);
-      RangeGuard rg("gs.prove.g1");
-      // (the fixed-base kernel reads X as the commitments' affine addend; the constants A only feed the variable-base one)
-      const unsigned masks[4] = {BIT(PI_X), BIT(PI_A), BIT(PO_XC), BIT(PO_TH)};
-      RC((run_side<C, F1>(c, ".g1", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs,
-                          ov ? c->side[1] : nullptr, c->sev[1], c->sev[2], masks)));
-      return GS_OK;
-    };
     // G2 side: ycoms (n) + pi (kx).  constants B (len m) multiply R; Psi multiplies Y; fixed part Omega.
-    auto side_g2 = [&]() -> int {
+    auto side = [&](auto* ftag) -> int {
+      typedef std::remove_pointer_t<decltype(ftag)> F;
+      constexpr bool g2 = std::is_same<F, F2>::value;
+      const bool grp = g2 ? yg : xg;
+      const int nv = g2 ? n : m, nc = g2 ? m : n, kc = g2 ? ky : kx, npf = g2 ? kx : ky;
+      const size_t zp = g2 ? Z::G2 : Z::G1;
+      void* coms = g2 ? ycoms : xcoms;
       SidePlan sp;
-      sp.tm = yg ? pick_tm(c, fillN(c, N), m + n, kx, true, kx) : 1;
-      build_side(sp, ycoms != nullptr, n, m, yg, ky, kx, pm.SC, pm.YC, pm.RC, pm.PSI, pm.OM, pm.RHO);
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      if (yg) {
-        arrs.base[0] = (const uint8_t*)Y;
-        arrs.stride[0] = shared ? 0u : (uint32_t)(n * Z::G2);
-        arrs.base[1] = (const uint8_t*)B;
-        arrs.stride[1] = (uint32_t)(m * Z::G2);
-      }
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)ycoms;
-      outs.stride[0] = (uint32_t)(n * Z::COM2);
-      outs.base[1] = (uint8_t*)pi;
-      outs.stride[1] = (uint32_t)(kx * Z::COM2);
-      if (ov) c->cur = c->side[0];  // the whole G2 side runs beside the G1 side
-      RangeGuard rg("gs.prove.g2");
-      const unsigned masks[4] = {BIT(PI_Y), BIT(PI_B), BIT(PO_YC), BIT(PO_PI)};
-      RC((run_side<C, F2>(c, ".g2", N, sp, arrs, (const S*)pool, pm.total, (const A2*)c->tabs->tab16_g2.p, outs,
-                          ov ? c->side[2] : nullptr, c->sev[3], c->sev[4], masks)));
-      if (ov) {
+      sp.tm = grp ? pick_tm(c, fillN(c, N), m + n, npf, g2, npf) : 1;
+      if (g2)
+        build_side(sp, coms != nullptr, nv, nc, grp, kc, npf, pm.SC, pm.YC, pm.RC, pm.PSI, pm.OM, pm.RHO);
+      else
+        build_side(sp, coms != nullptr, nv, nc, grp, kc, npf, pm.RC, pm.XC, pm.SC, pm.PHI, pm.TC, pm.SIG);
+      const ArrTab arrs = arr_tab({{0, g2 ? Y : X, shared ? 0u : (uint32_t)(nv * zp), grp},
+                                   {1, g2 ? B : A, (uint32_t)(nc * zp), grp}});
+      const OutTab outs = out_tab(coms, (uint32_t)(nv * 2 * zp), g2 ? pi : theta, (uint32_t)(npf * 2 * zp));
+      if (g2 && ov) c->cur = c->side[0];  // the whole G2 side runs beside the G1 side
+      RangeGuard rg(g2 ? "gs.prove.g2" : "gs.prove.g1");
+      // (the fixed-base kernel reads the variables as the commitments' affine addend; the constants only feed the
+      // variable-base one)
+      const unsigned masks[4] = {BIT(g2 ? PI_Y : PI_X), BIT(g2 ? PI_B : PI_A), BIT(g2 ? PO_YC : PO_XC),
+                                 BIT(g2 ? PO_PI : PO_TH)};
+      const void* tab = g2 ? c->tabs->tab16_g2.p : c->tabs->tab16_g1.p;
+      // the side's variable-base kernel forks to side[1] (events 1, 2) on G1, to side[2] (events 3, 4) on G2
+      RC((run_side<C, F>(c, g2 ? ".g2" : ".g1", N, sp, arrs, (const S*)pool, pm.total, (const Aff<F>*)tab, outs,
+                         ov ? c->side[g2 ? 2 : 1] : nullptr, c->sev[g2 ? 3 : 1], c->sev[g2 ? 4 : 2], masks)));
+      if (g2 && ov) {  // join
         hipEventRecord(c->sev[5], c->side[0]);
         c->cur = nullptr;
         hipStreamWaitEvent(c->stream, c->sev[5], 0);
@@ -1705,13 +1754,10 @@ template <class C> struct Impl {
     // A host-pointer call runs the G2 side FIRST: every output but the last proof element crosses PCIe under later
     // kernels (the commitments of a side under its variable-base kernel, the first side's proof element under the second
     // side), and the one that is left after the last kernel is then theta (1/8 of the output bytes) rather than pi.
-    if (c->pipe && !ov && N >= 16 * c->simd_slots) {
-      RC(side_g2());
-      RC(side_g1());
-    } else {
-      RC(side_g1());
-      RC(side_g2());
-    }
+    const bool g2_first = c->pipe && !ov && N >= 16 * c->simd_slots;
+    if (!g2_first) RC(side((F1*)nullptr));
+    RC(side((F2*)nullptr));
+    if (g2_first) RC(side((F1*)nullptr));
     return GS_OK;
   }
 
@@ -1732,20 +1778,8 @@ template <class C> struct Impl {
     RC(scratch(c, "rerand.pool", N * pm.total * sizeof(S), &pool));
     RangeGuard rg_all("gs.rerandomize");
     RC(need(c, BIT(RI_G) | BIT(RI_R) | BIT(RI_S) | BIT(RI_T) | (xg ? 0u : BIT(RI_A)) | (yg ? 0u : BIT(RI_B))));
-    if (wide_prep(m, n)) {
-      int W = m * kx + n * ky + ky * kx + m + n + kx * n + ky * m;
-      RC(launch_seg<k_prep_prove_wide_a<C>>(c, "k_prep_rerand.a", N * (size_t)W, 64, N * (size_t)W, W, m, n, kx, ky,
-                (const S*)G, (const S*)R, (const S*)Sm, (const S*)T, (const S*)nullptr, (const S*)nullptr, pm, (S*)pool,
-                shared ? 1 : 0));
-      size_t tb = N * (size_t)(kx * ky + kx + ky);
-      RC(launch_seg<k_prep_prove_wide_b<C>>(c, "k_prep_rerand.b", tb, 64, tb, m, n, kx, ky, (const S*)R, (const S*)Sm,
-                (const S*)T, (const S*)nullptr, (const S*)nullptr, xg ? nullptr : (const S*)A,
-                yg ? nullptr : (const S*)B, pm, (S*)pool, shared ? 1 : 0));
-    } else {
-      RC(launch_seg<k_prep_prove<C>>(c, "k_prep_rerand", N, 64, N, m, n, kx, ky, (const S*)G, (const S*)R, (const S*)Sm,
-                (const S*)T, (const S*)nullptr, (const S*)nullptr, xg ? nullptr : (const S*)A,
-                yg ? nullptr : (const S*)B, pm, (S*)pool, shared ? 1 : 0));
-    }
+    RC(prep_prove(c, "k_prep_rerand", N, m, n, kx, ky, G, R, Sm, T, nullptr, nullptr, xg ? nullptr : A, yg ? nullptr : B,
+                  pm, pool, shared));
     // one side over NN equations: the commitments (coms) and / or the proof elements (proofs) of that side
     auto side = [&](auto* ftag, size_t NN, bool coms, bool proofs, const char* tag) -> int {
       typedef std::remove_pointer_t<decltype(ftag)> F;
@@ -1759,22 +1793,10 @@ template <class C> struct Impl {
         build_rerand_side(sp, coms, nv, nc, grp, kc, np, pm.SC, pm.RC, pm.PSI, pm.OM, pm.RHO);
       else
         build_rerand_side(sp, coms, nv, nc, grp, kc, np, pm.RC, pm.SC, pm.PHI, pm.TC, pm.SIG);
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      arrs.base[0] = (const uint8_t*)(g2 ? yc : xc);
-      arrs.stride[0] = shared ? 0u : (uint32_t)nv * 2 * zp;
-      if (grp) {
-        arrs.base[1] = (const uint8_t*)(g2 ? B : A);
-        arrs.stride[1] = (uint32_t)nc * zp;
-      }
-      arrs.base[2] = (const uint8_t*)(g2 ? pi : th);
-      arrs.stride[2] = (uint32_t)npf * 2 * zp;
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)(g2 ? yco : xco);
-      outs.stride[0] = (uint32_t)nv * 2 * zp;
-      outs.base[1] = (uint8_t*)(g2 ? pio : tho);
-      outs.stride[1] = (uint32_t)npf * 2 * zp;
+      const ArrTab arrs = arr_tab({{0, g2 ? yc : xc, shared ? 0u : (uint32_t)nv * 2 * zp},
+                                   {1, g2 ? B : A, (uint32_t)nc * zp, grp},
+                                   {2, g2 ? pi : th, (uint32_t)npf * 2 * zp}});
+      const OutTab outs = out_tab(g2 ? yco : xco, (uint32_t)nv * 2 * zp, g2 ? pio : tho, (uint32_t)npf * 2 * zp);
       RangeGuard rg(g2 ? "gs.rerandomize.g2" : "gs.rerandomize.g1");
       const unsigned in_com = BIT(g2 ? RI_YC : RI_XC), in_pf = BIT(g2 ? RI_PI : RI_TH), in_k = BIT(g2 ? RI_B : RI_A);
       const unsigned masks[4] = {in_com | (proofs ? in_pf : 0u), proofs ? in_k : 0u, coms ? BIT(g2 ? RO_YC : RO_XC) : 0u,
@@ -1817,16 +1839,8 @@ template <class C> struct Impl {
               (const S*)nullptr, (const S*)nullptr, pm, (S*)pool, 0));
     SidePlan sp;
     build_side(sp, true, 1, 0, group, kc, 0, pm.RC, pm.XC, 0, 0, 0, 0);
-    ArrTab arrs;
-    memset(&arrs, 0, sizeof arrs);
-    if (group) {
-      arrs.base[0] = (const uint8_t*)vars;
-      arrs.stride[0] = (uint32_t)bsz;
-    }
-    OutTab outs;
-    memset(&outs, 0, sizeof outs);
-    outs.base[0] = (uint8_t*)out;
-    outs.stride[0] = (uint32_t)(2 * bsz);
+    const ArrTab arrs = arr_tab({{0, vars, (uint32_t)bsz, group}});
+    const OutTab outs = out_tab(out, (uint32_t)(2 * bsz));
     return run_side<C, F>(c, tag, count, sp, arrs, (const S*)pool, pm.total, tab, outs);
   }
 
@@ -1837,17 +1851,6 @@ template <class C> struct Impl {
     CellMap cm;
     int npa;                          // Com1 elements in the PA scratch per equation
   };
-
-  static void add_pair(std::vector<PairRef>& v, int p_arr, int p_idx, int neg, int q_arr, int q_idx) {
-    PairRef r;
-    r.p_arr = (uint8_t)p_arr;
-    r.p_idx = (uint32_t)p_idx;
-    r.neg = (uint8_t)neg;
-    r.q_arr = (uint8_t)q_arr;
-    r.q_idx = (uint32_t)q_idx;
-    r.pad = 0;
-    v.push_back(r);
-  }
 
   // P arrays: 0 PA scratch, 1 xcoms, 2 crs G1 consts, 3 theta
   // Q arrays: 0 ycoms, 1 B, 2 crs G2 consts, 3 pi, 4 target (MSMEG2)
@@ -1866,43 +1869,27 @@ template <class C> struct Impl {
       sp.tm = 8;
       sp.tab_bases = 2 * m;
     }
-    int slot = 0;
-    for (int j = 0; j < n; j++) {
-      int b[2], e[2];
-      for (int a = 0; a < 2; a++) {
-        b[a] = slot;
-        if (xg) {
-          if (a == 1) sp.fix.push_back(mkfix(0, 0xFF, 0, 0xFF, 1, j, slot++));
-        } else {
-          sp.fix.push_back(mkfix(pm.AC + j, tb_w(a), 0, 0xFF, 0xFF, 0, slot++));
-        }
-        {
-          std::vector<VarTask> terms;
-          for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, 2 * i + a, 0));
-          add_var_terms(sp, terms, slot);
-        }
-        e[a] = slot;
-      }
-      sp.red.push_back(mkred(b[0], e[0], b[1], e[1], 0, j));
-    }
+    ComOutputs out{sp};
+    out.add(n, 0, 0, [&](int j, int a, ComOutputs& o) {
+      if (!xg)
+        o.fix(pm.AC + j, tb_w(a), 0, 0xFF, 0xFF, 0);
+      else if (a == 1)
+        o.fix(0, 0xFF, 0, 0xFF, 1, j);
+      std::vector<VarTask> terms;
+      for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, 2 * i + a, 0));
+      o.terms(terms);
+    });
     vp.npa = n;
     if (!yg) {
-      int b[2], e[2];
-      for (int a = 0; a < 2; a++) {
-        b[a] = slot;
-        {
-          std::vector<VarTask> terms;
-          for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.BC + i, 0, 2 * i + a, 0));
-          add_var_terms(sp, terms, slot);
-        }
-        if (ty == GS_MSMEG1 && a == 1) sp.fix.push_back(mkfix(0, 0xFF, 0, 0xFF, 2, 0, slot++, 1));  // - t
-        if (ty == GS_QUAD) sp.fix.push_back(mkfix(pm.NT, tb_w(a), 0, 0xFF, 0xFF, 0, slot++));       // (-t) W1.a
-        e[a] = slot;
-      }
-      sp.red.push_back(mkred(b[0], e[0], b[1], e[1], 0, n));
+      out.add(1, 0, n, [&](int, int a, ComOutputs& o) {
+        std::vector<VarTask> terms;
+        for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.BC + i, 0, 2 * i + a, 0));
+        o.terms(terms);
+        if (ty == GS_MSMEG1 && a == 1) o.fix(0, 0xFF, 0, 0xFF, 2, 0, 1);  // - t
+        if (ty == GS_QUAD) o.fix(pm.NT, tb_w(a), 0, 0xFF, 0xFF, 0);       // (-t) W1.a
+      });
       vp.npa = n + 1;
     }
-    sp.nslots = slot;
   }
   static void build_verify_miller(VerifyPlan& vp, int curve, int ty, int m, int n, double budget, bool twin, bool lt) {
     bool xg = x_is_group(ty), yg = y_is_group(ty);
@@ -1942,6 +1929,30 @@ template <class C> struct Impl {
     }
   }
 
+  // Gamma as k_prep_verify[_rlc] takes it.  Large arities bring it to canonical form in the pool first, one lane per
+  // entry, and the preparation kernel then leaves it alone (*g = null).
+  static int prep_gamma(gs_ctx* c, size_t N, int m, int n, const void* G, const PoolMap& pm, void* pool, const S** g) {
+    const bool wide = wide_prep(m, n);
+    *g = wide ? nullptr : (const S*)G;
+    if (!wide) return GS_OK;
+    return launch_seg<k_fr_canonical<C>>(c, "k_fr_canonical", N * (size_t)m * n, 64, N * (size_t)m * n, m * n, (const S*)G,
+              pm.total, (S*)pool + pm.GC);
+  }
+  // the line tables a Miller launch reads (null: every line is stepped)
+  static const Line<C>* lines(const gs_ctx* c) { return (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr); }
+  // Miller tail of the two RLC verifiers: the single-accumulator task list `mt` (plan_miller_single) goes up as `tag`.mt
+  // and runs as k_miller.`tag` into the scratch `tag`.mpart (mt.size() partials per equation).
+  static int miller_single(gs_ctx* c, const std::string& tag, size_t N, const std::vector<MillerTask>& mt,
+                           const ArrTab& parr, const ArrTab& qarr, void** mpart) {
+    const MillerTask* dmt;
+    RC(upload(c, (tag + ".mt").c_str(), mt, &dmt));
+    const int ntask = (int)mt.size();
+    RC(scratch(c, (tag + ".mpart").c_str(), N * ntask * sizeof(GT), mpart));
+    miller_work_hint(c, N, mt, false);
+    return launch_seg<k_miller<C, false>>(c, ("k_miller." + tag).c_str(), N * ntask, 64, N * ntask, ntask, dmt, parr, qarr,
+              (GT*)*mpart, 1, lines(c));
+  }
+
   // shared front of both verifier modes: G1-side points + Miller partials
   static int verify_front(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                           const void* target, const void* xcoms, const void* ycoms, const void* pi,
@@ -1959,13 +1970,10 @@ template <class C> struct Impl {
     void* pool;
     RC(scratch(c, "verify.pool", N * pm.total * sizeof(S), &pool));
     RC(need(c, BIT(VI_G) | (xg ? 0u : BIT(VI_A)) | (yg ? 0u : BIT(VI_B)) | (ty == GS_QUAD ? BIT(VI_TG) : 0u)));
-    const bool wide = wide_prep(m, n);
-    if (wide)
-      RC(launch_seg<k_fr_canonical<C>>(c, "k_fr_canonical", N * (size_t)m * n, 64, N * (size_t)m * n, m * n, (const S*)G,
-                pm.total, (S*)pool + pm.GC));
-    RC(launch_seg<k_prep_verify<C>>(c, "k_prep_verify", N, 64, N, m, n, wide ? nullptr : (const S*)G,
-              xg ? nullptr : (const S*)A, yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, pm,
-              (S*)pool));
+    const S* g;
+    RC(prep_gamma(c, N, m, n, G, pm, pool, &g));
+    RC(launch_seg<k_prep_verify<C>>(c, "k_prep_verify", N, 64, N, m, n, g, xg ? nullptr : (const S*)A,
+              yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, pm, (S*)pool));
     // lane shape for this batch size: single or twin accumulators (the twin task list on one lane with two
     // accumulators, or on a pair of lanes with one each), lane-cost budget (cost model above)
     int mode = 0;  // 0 single, 1 twin, 2 pair (LDS exchange), 3 pair (DPP exchange)
@@ -2018,22 +2026,11 @@ template <class C> struct Impl {
     void* pa;
     RC(scratch(c, "verify.pa", N * vp.npa * Z::COM1, &pa));
     {
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      arrs.base[0] = (const uint8_t*)xcoms;
-      arrs.stride[0] = shared ? 0u : (uint32_t)(m * Z::COM1);  // a Statement's equations share the commitments
-      if (xg) {
-        arrs.base[1] = (const uint8_t*)A;
-        arrs.stride[1] = (uint32_t)(n * Z::G1);
-      }
-      if (ty == GS_MSMEG1) {
-        arrs.base[2] = (const uint8_t*)target;
-        arrs.stride[2] = (uint32_t)Z::G1;
-      }
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)pa;
-      outs.stride[0] = (uint32_t)(vp.npa * Z::COM1);
+      // (a Statement's equations share the commitments)
+      const ArrTab arrs = arr_tab({{0, xcoms, shared ? 0u : (uint32_t)(m * Z::COM1)},
+                                   {1, A, (uint32_t)(n * Z::G1), xg},
+                                   {2, target, (uint32_t)Z::G1, ty == GS_MSMEG1}});
+      const OutTab outs = out_tab(pa, (uint32_t)(vp.npa * Z::COM1));
       RangeGuard rg("gs.verify.g1");
       RC(need(c, BIT(VI_XC) | BIT(VI_A) | BIT(VI_TG) * (ty == GS_MSMEG1 ? 1u : 0u)));
       RC((run_side<C, F1>(c, ".vg1", N, vp.g1, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
@@ -2046,35 +2043,16 @@ template <class C> struct Impl {
     int ntask = (int)vp.mt.size();
     void* mpart;
     RC(scratch(c, "verify.mpart", 2 * N * ntask * sizeof(GT), &mpart));
-    ArrTab parr, qarr;
-    memset(&parr, 0, sizeof parr);
-    memset(&qarr, 0, sizeof qarr);
-    parr.base[0] = (const uint8_t*)pa;
-    parr.stride[0] = (uint32_t)(vp.npa * Z::COM1);
-    parr.base[1] = (const uint8_t*)xcoms;
-    parr.stride[1] = shared ? 0u : (uint32_t)(m * Z::COM1);
-    parr.base[2] = (const uint8_t*)c->tabs->crs_g1.p;
-    parr.stride[2] = 0;
-    parr.base[3] = (const uint8_t*)theta;
-    parr.stride[3] = (uint32_t)(ky * Z::COM1);
-    qarr.base[0] = (const uint8_t*)ycoms;
-    qarr.stride[0] = shared ? 0u : (uint32_t)(n * Z::COM2);
-    qarr.base[1] = (const uint8_t*)B;
-    qarr.stride[1] = (uint32_t)(m * Z::G2);
-    qarr.base[2] = (const uint8_t*)c->tabs->crs_g2.p;
-    qarr.stride[2] = 0;
-    qarr.base[3] = (const uint8_t*)pi;
-    qarr.stride[3] = (uint32_t)(kx * Z::COM2);
-    qarr.base[4] = (const uint8_t*)target;
-    qarr.stride[4] = (uint32_t)Z::G2;
-    {
-      // (P, Q) pairs (twin: (Q, P0, P1) triples) per equation, a table-reading pair counted at its cost ratio
-      const MCost mc = mcost(c->curve, twin);
-      double pairs = 0;
-      for (const MillerTask& t : vp.mt)
-        for (int q = 0; q < t.np; q++) pairs += pair_fixed(c->line_tables, t.pr[q]) ? mc.fix / mc.var : 1.0;
-      c->work_hint = (uint64_t)((double)N * pairs);
-    }
+    const ArrTab parr = arr_tab({{0, pa, (uint32_t)(vp.npa * Z::COM1)},
+                                 {1, xcoms, shared ? 0u : (uint32_t)(m * Z::COM1)},
+                                 {2, c->tabs->crs_g1.p, 0},
+                                 {3, theta, (uint32_t)(ky * Z::COM1)}});
+    const ArrTab qarr = arr_tab({{0, ycoms, shared ? 0u : (uint32_t)(n * Z::COM2)},
+                                 {1, B, (uint32_t)(m * Z::G2)},
+                                 {2, c->tabs->crs_g2.p, 0},
+                                 {3, pi, (uint32_t)(kx * Z::COM2)},
+                                 {4, target, (uint32_t)Z::G2}});
+    miller_work_hint(c, N, vp.mt, twin);
     if (getenv("GS_PLAN_TRACE")) {
       const MCost mc = mcost(c->curve, twin);
       fprintf(stderr, "[plan] verify ty %d N %zu (fill %zu) m %d n %d: miller mode %d budget %.0f, %d tasks, lanes:", ty, N,
@@ -2088,16 +2066,16 @@ template <class C> struct Impl {
     }
     if (mode == 2)
       RC(launch_seg<k_miller_pair<C, false>>(c, "k_miller.pair", 2 * N * ntask, 64, 2 * N * ntask, ntask, dmt, parr, qarr,
-                (GT*)mpart, (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+                (GT*)mpart, lines(c)));
     else if (mode == 3)
       RC(launch_seg<k_miller_pair<C, true>>(c, "k_miller.pairdpp", 2 * N * ntask, 64, 2 * N * ntask, ntask, dmt, parr, qarr,
-                (GT*)mpart, (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+                (GT*)mpart, lines(c)));
     else if (twin)
       RC(launch_seg<k_miller<C, true>>(c, "k_miller.twin", N * ntask, 64, N * ntask, ntask, dmt, parr, qarr, (GT*)mpart, 2,
-                (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+                lines(c)));
     else
       RC(launch_seg<k_miller<C, false>>(c, "k_miller", N * ntask, 64, N * ntask, ntask, dmt, parr, qarr, (GT*)mpart, 2,
-                (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+                lines(c)));
     *mpart_out = mpart;
     return GS_OK;
   }
@@ -2194,13 +2172,10 @@ template <class C> struct Impl {
     pm.total = o;
     void* pool;
     RC(scratch(c, "rlc.pool", N * pm.total * sizeof(S), &pool));
-    const bool wide = wide_prep(m, n);
-    if (wide)
-      RC(launch_seg<k_fr_canonical<C>>(c, "k_fr_canonical", N * (size_t)m * n, 64, N * (size_t)m * n, m * n, (const S*)G,
-                pm.total, (S*)pool + pm.GC));
-    RC(launch(c, "k_prep_verify_rlc", k_prep_verify_rlc<C>, N, 64, N, m, n, wide ? nullptr : (const S*)G,
-              xg ? nullptr : (const S*)A, yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, rho,
-              pm, (S*)pool));
+    const S* g;
+    RC(prep_gamma(c, N, m, n, G, pm, pool, &g));
+    RC(launch(c, "k_prep_verify_rlc", k_prep_verify_rlc<C>, N, 64, N, m, n, g, xg ? nullptr : (const S*)A,
+              yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, rho, pm, (S*)pool));
     auto RH = [&](int a, int b) { return pm.RH + 2 * a + b; };
     // ---- pass 1
     int n1 = m + ky;
@@ -2209,30 +2184,12 @@ template <class C> struct Impl {
     {
       SidePlan sp;
       sp.tm = c->endo ? 4 : 1;  // endo = 0: one plain double-and-add lane per term ("k_var.plain"), as everywhere else
-      int slot = 0;
-      for (int q = 0; q < n1; q++) {
+      ComOutputs{sp}.add(n1, 0, 0, [&](int q, int b, ComOutputs& o) {
         int arr = q < m ? 0 : 1, idx = q < m ? q : q - m;
-        int b0 = slot, e0 = 0, b1 = 0;
-        for (int b = 0; b < 2; b++) {
-          if (b == 1) { e0 = slot; b1 = slot; }
-          std::vector<VarTask> terms;
-          terms.push_back(mkvar(RH(0, b), arr, 2 * idx, 0));
-          terms.push_back(mkvar(RH(1, b), arr, 2 * idx + 1, 0));
-          add_var_terms(sp, terms, slot);
-        }
-        sp.red.push_back(mkred(b0, e0, b1, slot, 0, q));
-      }
-      sp.nslots = slot;
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      arrs.base[0] = (const uint8_t*)xcoms;
-      arrs.stride[0] = (uint32_t)(m * Z::COM1);
-      arrs.base[1] = (const uint8_t*)theta;
-      arrs.stride[1] = (uint32_t)(ky * Z::COM1);
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)s1;
-      outs.stride[0] = (uint32_t)(n1 * Z::COM1);
+        o.terms({mkvar(RH(0, b), arr, 2 * idx, 0), mkvar(RH(1, b), arr, 2 * idx + 1, 0)});
+      });
+      const ArrTab arrs = arr_tab({{0, xcoms, (uint32_t)(m * Z::COM1)}, {1, theta, (uint32_t)(ky * Z::COM1)}});
+      const OutTab outs = out_tab(s1, (uint32_t)(n1 * Z::COM1));
       RC((run_side<C, F1>(c, ".r1", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
     // ---- pass 2: elements 0..n-1 = P'_j, then [PB'] , U'_k (kx), [W1'] (MSMEG2)
@@ -2242,54 +2199,35 @@ template <class C> struct Impl {
     {
       SidePlan sp;
       sp.tm = c->endo ? 8 : 1;
-      int slot = 0;
-      for (int q = 0; q < n2; q++) {
-        int b0 = slot, e0 = 0, b1 = 0;
-        for (int b = 0; b < 2; b++) {
-          if (b == 1) { e0 = slot; b1 = slot; }
-          std::vector<VarTask> terms;
-          if (q < n) {
-            int j = q;
-            if (xg)
-              terms.push_back(mkvar(RH(1, b), 1, j, 0));                                        // rho_1b A_j
-            else
-              sp.fix.push_back(mkfix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0, slot++));
-            for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, 2 * i + b, 0));  // Gamma_ij C'_ib
-          } else if (!yg && q == iPB) {
-            for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.BC + i, 0, 2 * i + b, 0));          // b_i C'_ib
-            if (ty == GS_MSMEG1) {
-              VarTask v = mkvar(RH(1, b), 2, 0, 0);                                                  // - rho_1b t
-              v.neg = 1;
-              terms.push_back(v);
-            }
-            if (ty == GS_QUAD) sp.fix.push_back(mkfix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0, slot++));
-          } else if (q >= iU && q < iU + kx) {
-            int k = q - iU;
-            sp.fix.push_back(mkfix(RH(0, b), tb_u(k, 0), RH(1, b), tb_u(k, 1), 0xFF, 0, slot++));
-          } else {  // W1' (MSMEG2)
-            sp.fix.push_back(mkfix(RH(0, b), tb_w(0), RH(1, b), tb_w(1), 0xFF, 0, slot++));
+      ComOutputs{sp}.add(n2, 0, 0, [&](int q, int b, ComOutputs& o) {
+        std::vector<VarTask> terms;
+        if (q < n) {
+          int j = q;
+          if (xg)
+            terms.push_back(mkvar(RH(1, b), 1, j, 0));                                        // rho_1b A_j
+          else
+            o.fix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0);
+          for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, 2 * i + b, 0));  // Gamma_ij C'_ib
+        } else if (!yg && q == iPB) {
+          for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.BC + i, 0, 2 * i + b, 0));          // b_i C'_ib
+          if (ty == GS_MSMEG1) {
+            VarTask v = mkvar(RH(1, b), 2, 0, 0);                                                  // - rho_1b t
+            v.neg = 1;
+            terms.push_back(v);
           }
-          if (!terms.empty()) add_var_terms(sp, terms, slot);
+          if (ty == GS_QUAD) o.fix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0);
+        } else if (q >= iU && q < iU + kx) {
+          int k = q - iU;
+          o.fix(RH(0, b), tb_u(k, 0), RH(1, b), tb_u(k, 1), 0xFF, 0);
+        } else {  // W1' (MSMEG2)
+          o.fix(RH(0, b), tb_w(0), RH(1, b), tb_w(1), 0xFF, 0);
         }
-        sp.red.push_back(mkred(b0, e0, b1, slot, 0, q));
-      }
-      sp.nslots = slot;
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      arrs.base[0] = (const uint8_t*)s1;
-      arrs.stride[0] = (uint32_t)(n1 * Z::COM1);
-      if (xg) {
-        arrs.base[1] = (const uint8_t*)A;
-        arrs.stride[1] = (uint32_t)(n * Z::G1);
-      }
-      if (ty == GS_MSMEG1) {
-        arrs.base[2] = (const uint8_t*)target;
-        arrs.stride[2] = (uint32_t)Z::G1;
-      }
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)s2;
-      outs.stride[0] = (uint32_t)(n2 * Z::COM1);
+        o.terms(terms);
+      });
+      const ArrTab arrs = arr_tab({{0, s1, (uint32_t)(n1 * Z::COM1)},
+                                   {1, A, (uint32_t)(n * Z::G1), xg},
+                                   {2, target, (uint32_t)Z::G1, ty == GS_MSMEG1}});
+      const OutTab outs = out_tab(s2, (uint32_t)(n2 * Z::COM1));
       RC((run_side<C, F1>(c, ".r2", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
     // ---- Miller: every G2 argument once.  P arrays: 0 = S2, 1 = S1.  Q arrays: 0 ycoms, 1 B, 2 crs, 3 pi, 4 target
@@ -2306,51 +2244,18 @@ template <class C> struct Impl {
       for (int l = 0; l < ky; l++) add_pair(pr, 1, 2 * (m + l) + b, 1, 2, 2 * l + b);
       if (ty == GS_MSMEG2 && b == 1) add_pair(pr, 0, 2 * iW + 1, 1, 4, 0);
     }
-    std::vector<MillerTask> mt;
-    {
-      double best = -1;
-      for (double cand : miller_budgets(c, false)) {
-        std::vector<MillerTask> tmp;
-        chunk_tasks(tmp, pr, cand, 0, true, mcost(c->curve, false), c->line_tables);
-        double cost = miller_cost(c, N, tmp, false);
-        if (best < 0 || cost < best) {
-          best = cost;
-          mt = tmp;
-        }
-      }
-    }
-    const MillerTask* dmt;
-    RC(upload(c, "rlc.mt", mt, &dmt));
-    int ntask = (int)mt.size();
+    const ArrTab parr = arr_tab({{0, s2, (uint32_t)(n2 * Z::COM1)}, {1, s1, (uint32_t)(n1 * Z::COM1)}});
+    const ArrTab qarr = arr_tab({{0, ycoms, (uint32_t)(n * Z::COM2)},
+                                 {1, B, (uint32_t)(m * Z::G2)},
+                                 {2, c->tabs->crs_g2.p, 0},
+                                 {3, pi, (uint32_t)(kx * Z::COM2)},
+                                 {4, target, (uint32_t)Z::G2}});
+    const std::vector<MillerTask> mt = plan_miller_single(c, N, pr);
+    const int ntask = (int)mt.size();
     void *mpart, *pt, *tmp;
-    RC(scratch(c, "rlc.mpart", N * ntask * sizeof(GT), &mpart));
     RC(scratch(c, "rlc.t", (N + 1) * sizeof(GT), &pt));
     RC(scratch(c, "rlc.tmp", (N * ntask / 4 + 8) * sizeof(GT), &tmp));
-    ArrTab parr, qarr;
-    memset(&parr, 0, sizeof parr);
-    memset(&qarr, 0, sizeof qarr);
-    parr.base[0] = (const uint8_t*)s2;
-    parr.stride[0] = (uint32_t)(n2 * Z::COM1);
-    parr.base[1] = (const uint8_t*)s1;
-    parr.stride[1] = (uint32_t)(n1 * Z::COM1);
-    qarr.base[0] = (const uint8_t*)ycoms;
-    qarr.stride[0] = (uint32_t)(n * Z::COM2);
-    qarr.base[1] = (const uint8_t*)B;
-    qarr.stride[1] = (uint32_t)(m * Z::G2);
-    qarr.base[2] = (const uint8_t*)c->tabs->crs_g2.p;
-    qarr.base[3] = (const uint8_t*)pi;
-    qarr.stride[3] = (uint32_t)(kx * Z::COM2);
-    qarr.base[4] = (const uint8_t*)target;
-    qarr.stride[4] = (uint32_t)Z::G2;
-    {
-      const MCost mc = mcost(c->curve, false);
-      double pairs = 0;
-      for (const MillerTask& t : mt)
-        for (int q = 0; q < t.np; q++) pairs += pair_fixed(c->line_tables, t.pr[q]) ? mc.fix / mc.var : 1.0;
-      c->work_hint = (uint64_t)((double)N * pairs);
-    }
-    RC(launch_seg<k_miller<C, false>>(c, "k_miller.rlc", N * ntask, 64, N * ntask, ntask, dmt, parr, qarr, (GT*)mpart, 1,
-              (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+    RC(miller_single(c, "rlc", N, mt, parr, qarr, &mpart));
     uint8_t* a = (uint8_t*)acc;
     RC(gt_product(c, N * ntask, (GT*)mpart, (GT*)tmp, a));
     if (ty == GS_PPE) {
@@ -2414,59 +2319,39 @@ template <class C> struct Impl {
     {
       SidePlan sp;
       sp.tm = tm;
-      int slot = 0;
-      for (int q = 0; q < n1; q++) {
-        int b0 = slot, e0 = 0, b1 = 0;
-        for (int b = 0; b < 2; b++) {
-          if (b == 1) { e0 = slot; b1 = slot; }
-          std::vector<VarTask> shortt, full;
-          if (q < n) {
-            const int j = q;
-            if (xg)
-              for (int e = 0; e < E; e++) shortt.push_back(mkvar(RH(e, 1, b), 1, e * n + j, 0));
-            else
-              sp.fix.push_back(mkfix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0, slot++));
-            for (int i = 0; i < m; i++)
-              for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.GC + ((2 * a + b) * m + i) * n + j, 0, 2 * i + a, 0));
-          } else if (!yg && q == iPB) {
-            for (int i = 0; i < m; i++)
-              for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.BC + i * 4 + 2 * a + b, 0, 2 * i + a, 0));
-            if (ty == GS_MSMEG1)
-              for (int e = 0; e < E; e++) {
-                VarTask v = mkvar(RH(e, 1, b), 2, e, 0);
-                v.neg = 1;
-                shortt.push_back(v);
-              }
-            if (ty == GS_QUAD) sp.fix.push_back(mkfix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0, slot++));
-          } else {
-            const int l = q - iTh;
-            for (int e = 0; e < E; e++)
-              for (int a = 0; a < 2; a++) shortt.push_back(mkvar(RH(e, a, b), 3, 2 * (e * ky + l) + a, 0));
-          }
-          add_var_terms(sp, shortt, slot);
-          add_var_terms(sp, full, slot);
+      ComOutputs{sp}.add(n1, 0, 0, [&](int q, int b, ComOutputs& o) {
+        std::vector<VarTask> shortt, full;
+        if (q < n) {
+          const int j = q;
+          if (xg)
+            for (int e = 0; e < E; e++) shortt.push_back(mkvar(RH(e, 1, b), 1, e * n + j, 0));
+          else
+            o.fix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0);
+          for (int i = 0; i < m; i++)
+            for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.GC + ((2 * a + b) * m + i) * n + j, 0, 2 * i + a, 0));
+        } else if (!yg && q == iPB) {
+          for (int i = 0; i < m; i++)
+            for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.BC + i * 4 + 2 * a + b, 0, 2 * i + a, 0));
+          if (ty == GS_MSMEG1)
+            for (int e = 0; e < E; e++) {
+              VarTask v = mkvar(RH(e, 1, b), 2, e, 0);
+              v.neg = 1;
+              shortt.push_back(v);
+            }
+          if (ty == GS_QUAD) o.fix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0);
+        } else {
+          const int l = q - iTh;
+          for (int e = 0; e < E; e++)
+            for (int a = 0; a < 2; a++) shortt.push_back(mkvar(RH(e, a, b), 3, 2 * (e * ky + l) + a, 0));
         }
-        sp.red.push_back(mkred(b0, e0, b1, slot, 0, q));
-      }
-      sp.nslots = slot;
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      arrs.base[0] = (const uint8_t*)xcoms;
-      arrs.stride[0] = (uint32_t)(m * Z::COM1);
-      if (xg) {
-        arrs.base[1] = (const uint8_t*)A;
-        arrs.stride[1] = (uint32_t)((size_t)E * n * Z::G1);
-      }
-      if (ty == GS_MSMEG1) {
-        arrs.base[2] = (const uint8_t*)target;
-        arrs.stride[2] = (uint32_t)((size_t)E * Z::G1);
-      }
-      arrs.base[3] = (const uint8_t*)theta;
-      arrs.stride[3] = (uint32_t)((size_t)E * ky * Z::COM1);
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)s1;
-      outs.stride[0] = (uint32_t)(n1 * Z::COM1);
+        o.terms(shortt);
+        o.terms(full);
+      });
+      const ArrTab arrs = arr_tab({{0, xcoms, (uint32_t)(m * Z::COM1)},
+                                   {1, A, (uint32_t)((size_t)E * n * Z::G1), xg},
+                                   {2, target, (uint32_t)((size_t)E * Z::G1), ty == GS_MSMEG1},
+                                   {3, theta, (uint32_t)((size_t)E * ky * Z::COM1)}});
+      const OutTab outs = out_tab(s1, (uint32_t)(n1 * Z::COM1));
       RC((run_side<C, F1>(c, ".s1", S, sp, arrs, (const Fr<C>*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
     // ---- G2 pass: elements [Q_i (m)], Pi_k (kx), [T] (MSMEG2).  Arrays: 0 B, 1 pi, 2 target (MSMEG2)
@@ -2476,42 +2361,23 @@ template <class C> struct Impl {
     {
       SidePlan sp;
       sp.tm = tm;
-      int slot = 0;
-      for (int q = 0; q < n2; q++) {
-        int b0 = slot, e0 = 0, b1 = 0;
-        for (int a = 0; a < 2; a++) {
-          if (a == 1) { e0 = slot; b1 = slot; }
-          std::vector<VarTask> terms;
-          if (q < iPi) {
-            for (int e = 0; e < E; e++) terms.push_back(mkvar(RH(e, a, 1), 0, e * m + q, 0));
-          } else if (q < iT) {
-            const int k = q - iPi;
-            for (int e = 0; e < E; e++)
-              for (int b = 0; b < 2; b++) terms.push_back(mkvar(RH(e, a, b), 1, 2 * (e * kx + k) + b, 0));
-          } else {
-            for (int e = 0; e < E; e++) terms.push_back(mkvar(RH(e, a, 1), 2, e, 0));
-          }
-          add_var_terms(sp, terms, slot);
+      ComOutputs{sp}.add(n2, 0, 0, [&](int q, int a, ComOutputs& o) {
+        std::vector<VarTask> terms;
+        if (q < iPi) {
+          for (int e = 0; e < E; e++) terms.push_back(mkvar(RH(e, a, 1), 0, e * m + q, 0));
+        } else if (q < iT) {
+          const int k = q - iPi;
+          for (int e = 0; e < E; e++)
+            for (int b = 0; b < 2; b++) terms.push_back(mkvar(RH(e, a, b), 1, 2 * (e * kx + k) + b, 0));
+        } else {
+          for (int e = 0; e < E; e++) terms.push_back(mkvar(RH(e, a, 1), 2, e, 0));
         }
-        sp.red.push_back(mkred(b0, e0, b1, slot, 0, q));
-      }
-      sp.nslots = slot;
-      ArrTab arrs;
-      memset(&arrs, 0, sizeof arrs);
-      if (yg) {
-        arrs.base[0] = (const uint8_t*)B;
-        arrs.stride[0] = (uint32_t)((size_t)E * m * Z::G2);
-      }
-      arrs.base[1] = (const uint8_t*)pi;
-      arrs.stride[1] = (uint32_t)((size_t)E * kx * Z::COM2);
-      if (ty == GS_MSMEG2) {
-        arrs.base[2] = (const uint8_t*)target;
-        arrs.stride[2] = (uint32_t)((size_t)E * Z::G2);
-      }
-      OutTab outs;
-      memset(&outs, 0, sizeof outs);
-      outs.base[0] = (uint8_t*)s2;
-      outs.stride[0] = (uint32_t)(n2 * Z::COM2);
+        o.terms(terms);
+      });
+      const ArrTab arrs = arr_tab({{0, B, (uint32_t)((size_t)E * m * Z::G2), yg},
+                                   {1, pi, (uint32_t)((size_t)E * kx * Z::COM2)},
+                                   {2, target, (uint32_t)((size_t)E * Z::G2), ty == GS_MSMEG2}});
+      const OutTab outs = out_tab(s2, (uint32_t)(n2 * Z::COM2));
       RC((run_side<C, F2>(c, ".s2", S, sp, arrs, (const Fr<C>*)pool, pm.total, (const A2*)c->tabs->tab16_g2.p, outs)));
     }
     // ---- Miller.  P arrays: 0 = S1, 1 = xcoms, 2 = crs G1 (u, W1).  Q arrays: 0 ycoms, 1 = S2, 2 = crs G2 (v, W2)
@@ -2527,46 +2393,12 @@ template <class C> struct Impl {
       for (int k = 0; k < kx; k++) add_pair(pr, 2, 2 * k + a, 1, 1, 2 * (iPi + k) + a);   // (-u_k.a, Pi_k.a)
       if (ty == GS_MSMEG2) add_pair(pr, 2, 4 + a, 1, 1, 2 * iT + a);                      // (-W1.a, T.a)
     }
-    std::vector<MillerTask> mt;
-    {
-      double best = -1;
-      for (double cand : miller_budgets(c, false)) {
-        std::vector<MillerTask> tmp;
-        chunk_tasks(tmp, pr, cand, 0, true, mcost(c->curve, false), c->line_tables);
-        double cost = miller_cost(c, S, tmp, false);
-        if (best < 0 || cost < best) {
-          best = cost;
-          mt = tmp;
-        }
-      }
-    }
-    const MillerTask* dmt;
-    RC(upload(c, "srlc.mt", mt, &dmt));
+    const std::vector<MillerTask> mt = plan_miller_single(c, S, pr);
     const int ntask = (int)mt.size();
+    const ArrTab parr = arr_tab({{0, s1, (uint32_t)(n1 * Z::COM1)}, {1, xcoms, (uint32_t)(m * Z::COM1)}, {2, c->tabs->crs_g1.p, 0}});
+    const ArrTab qarr = arr_tab({{0, ycoms, (uint32_t)(n * Z::COM2)}, {1, s2, (uint32_t)(n2 * Z::COM2)}, {2, c->tabs->crs_g2.p, 0}});
     void* mpart;
-    RC(scratch(c, "srlc.mpart", S * ntask * sizeof(GT), &mpart));
-    ArrTab parr, qarr;
-    memset(&parr, 0, sizeof parr);
-    memset(&qarr, 0, sizeof qarr);
-    parr.base[0] = (const uint8_t*)s1;
-    parr.stride[0] = (uint32_t)(n1 * Z::COM1);
-    parr.base[1] = (const uint8_t*)xcoms;
-    parr.stride[1] = (uint32_t)(m * Z::COM1);
-    parr.base[2] = (const uint8_t*)c->tabs->crs_g1.p;
-    qarr.base[0] = (const uint8_t*)ycoms;
-    qarr.stride[0] = (uint32_t)(n * Z::COM2);
-    qarr.base[1] = (const uint8_t*)s2;
-    qarr.stride[1] = (uint32_t)(n2 * Z::COM2);
-    qarr.base[2] = (const uint8_t*)c->tabs->crs_g2.p;
-    {
-      const MCost mc = mcost(c->curve, false);
-      double pairs = 0;
-      for (const MillerTask& t : mt)
-        for (int q = 0; q < t.np; q++) pairs += pair_fixed(c->line_tables, t.pr[q]) ? mc.fix / mc.var : 1.0;
-      c->work_hint = (uint64_t)((double)S * pairs);
-    }
-    RC(launch_seg<k_miller<C, false>>(c, "k_miller.srlc", S * ntask, 64, S * ntask, ntask, dmt, parr, qarr, (GT*)mpart, 1,
-              (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr)));
+    RC(miller_single(c, "srlc", S, mt, parr, qarr, &mpart));
     // ---- PPE: T_s = prod_e t_e^rho_e,11 (segmented K-ary product of k_rlc_tpow's S E powers)
     const GT* tprod = nullptr;
     if (ty == GS_PPE) {
@@ -2741,13 +2573,8 @@ static int left_mul_impl(gs_ctx* c, int rows, int k, const void* lhs, const void
     sp.red.push_back(mkred(b[0], e[0], b[1], e[1], 0, i));
   }
   sp.nslots = slot;
-  ArrTab arrs;
-  memset(&arrs, 0, sizeof arrs);
-  arrs.base[0] = (const uint8_t*)dc;
-  OutTab outs;
-  memset(&outs, 0, sizeof outs);
-  outs.base[0] = (uint8_t*)dout;
-  RC((run_side<C, F>(c, ".lm", 1, sp, arrs, (const S*)pool, pm.total, (const Aff<F>*)nullptr, outs)));
+  RC((run_side<C, F>(c, ".lm", 1, sp, arr_tab({{0, dc, 0}}), (const S*)pool, pm.total, (const Aff<F>*)nullptr,
+                     out_tab(dout, 0))));
   return st.back(out, dout, (size_t)rows * com);
 }
 
@@ -3821,6 +3648,20 @@ static int dlog_host(gs_ctx* c, const char* fn, int gi, bool coms, size_t n, con
   RC(st.back(out, dout, n * SZ_FR));
   return st.back(found, dfound, n);
 }
+// k P for n points of G1 (FT = Fq) or G2 (FT = Fp2), `grp` = ".g1" / ".g2"
+template <template <class> class FT>
+static int mul_batch_dev(gs_ctx* c, const char* grp, size_t n, const void* p, int bc, const void* k, void* out) {
+  RC(check_ctx(c, false));
+  if (n == 0) return GS_OK;
+  typedef Bls12_381 C0;
+  typedef Bn254 C1;
+  const std::string name = std::string(c->endo ? "k_smul_batch" : "k_smul_batch.plain") + grp;
+  auto go = [&](auto kern, auto* s) { return launch(c, name.c_str(), kern, n, 64, n, (const uint8_t*)p, bc, s, (uint8_t*)out); };
+  if (!c->endo)  // plain double-and-add lanes: any curve point (gs_set_option "endo" 0)
+    return c->curve == 0 ? go(k_smul_batch<C0, FT<C0>, false>, (const Fr<C0>*)k)
+                         : go(k_smul_batch<C1, FT<C1>, false>, (const Fr<C1>*)k);
+  return c->curve == 0 ? go(k_smul_batch<C0, FT<C0>>, (const Fr<C0>*)k) : go(k_smul_batch<C1, FT<C1>>, (const Fr<C1>*)k);
+}
 extern "C" {
 int gs_dlog_prepare(gs_ctx* c, int group, const void* base_host, unsigned log2_table) {
   RC(check_ctx(c, false));
@@ -3865,58 +3706,27 @@ int gs_extract_scalar_b2(gs_ctx* c, size_t n, const void* coms, unsigned bits, v
 
 // ---- helpers / hooks -----------------------------------------------------------
 int gs_g1_mul_batch_dev(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {
-  RC(check_ctx(c, false));
-  if (n == 0) return GS_OK;
-  if (!c->endo) {  // plain double-and-add lanes: any curve point (gs_set_option "endo" 0)
-    if (c->curve == 0)
-      return launch(c, "k_smul_batch.plain.g1", k_smul_batch<Bls12_381, Fq<Bls12_381>, false>, n, 64, n, (const uint8_t*)p,
-                    bc, (const Fr<Bls12_381>*)k, (uint8_t*)out);
-    return launch(c, "k_smul_batch.plain.g1", k_smul_batch<Bn254, Fq<Bn254>, false>, n, 64, n, (const uint8_t*)p, bc,
-                  (const Fr<Bn254>*)k, (uint8_t*)out);
-  }
-  if (c->curve == 0)
-    return launch(c, "k_smul_batch.g1", k_smul_batch<Bls12_381, Fq<Bls12_381>>, n, 64, n, (const uint8_t*)p, bc,
-                  (const Fr<Bls12_381>*)k, (uint8_t*)out);
-  return launch(c, "k_smul_batch.g1", k_smul_batch<Bn254, Fq<Bn254>>, n, 64, n, (const uint8_t*)p, bc,
-                (const Fr<Bn254>*)k, (uint8_t*)out);
+  return mul_batch_dev<Fq>(c, ".g1", n, p, bc, k, out);
 }
 int gs_g2_mul_batch_dev(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {
+  return mul_batch_dev<Fp2>(c, ".g2", n, p, bc, k, out);
+}
+static int mul_batch_host(gs_ctx* c, bool g2, size_t n, const void* p, int bc, const void* k, void* out) {
   RC(check_ctx(c, false));
-  if (n == 0) return GS_OK;
-  if (!c->endo) {  // plain double-and-add lanes: any curve point (gs_set_option "endo" 0)
-    if (c->curve == 0)
-      return launch(c, "k_smul_batch.plain.g2", k_smul_batch<Bls12_381, Fp2<Bls12_381>, false>, n, 64, n, (const uint8_t*)p,
-                    bc, (const Fr<Bls12_381>*)k, (uint8_t*)out);
-    return launch(c, "k_smul_batch.plain.g2", k_smul_batch<Bn254, Fp2<Bn254>, false>, n, 64, n, (const uint8_t*)p, bc,
-                  (const Fr<Bn254>*)k, (uint8_t*)out);
-  }
-  if (c->curve == 0)
-    return launch(c, "k_smul_batch.g2", k_smul_batch<Bls12_381, Fp2<Bls12_381>>, n, 64, n, (const uint8_t*)p, bc,
-                  (const Fr<Bls12_381>*)k, (uint8_t*)out);
-  return launch(c, "k_smul_batch.g2", k_smul_batch<Bn254, Fp2<Bn254>>, n, 64, n, (const uint8_t*)p, bc,
-                (const Fr<Bn254>*)k, (uint8_t*)out);
+  const size_t pt = (g2 ? 4 : 2) * sz_fq(c->curve);  // boundary bytes of one point
+  HostStage st(c);
+  void *dp, *dk, *dout;
+  RC(st.in(p, (bc ? 1 : n) * pt, &dp));
+  RC(st.in(k, n * SZ_FR, &dk));
+  RC(st.out(out, n * pt, &dout));
+  RC(g2 ? gs_g2_mul_batch_dev(c, n, dp, bc, dk, dout) : gs_g1_mul_batch_dev(c, n, dp, bc, dk, dout));
+  return st.back(out, dout, n * pt);
 }
 int gs_g1_mul_batch(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {
-  RC(check_ctx(c, false));
-  size_t fq = sz_fq(c->curve);
-  HostStage st(c);
-  void *dp, *dk, *dout;
-  RC(st.in(p, (bc ? 1 : n) * 2 * fq, &dp));
-  RC(st.in(k, n * SZ_FR, &dk));
-  RC(st.out(out, n * 2 * fq, &dout));
-  RC(gs_g1_mul_batch_dev(c, n, dp, bc, dk, dout));
-  return st.back(out, dout, n * 2 * fq);
+  return mul_batch_host(c, false, n, p, bc, k, out);
 }
 int gs_g2_mul_batch(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {
-  RC(check_ctx(c, false));
-  size_t fq = sz_fq(c->curve);
-  HostStage st(c);
-  void *dp, *dk, *dout;
-  RC(st.in(p, (bc ? 1 : n) * 4 * fq, &dp));
-  RC(st.in(k, n * SZ_FR, &dk));
-  RC(st.out(out, n * 4 * fq, &dout));
-  RC(gs_g2_mul_batch_dev(c, n, dp, bc, dk, dout));
-  return st.back(out, dout, n * 4 * fq);
+  return mul_batch_host(c, true, n, p, bc, k, out);
 }
 
 int gs_multi_pairing_batch_dev(gs_ctx* c, size_t n, int k, const void* p, const void* q, void* out) {
@@ -3965,10 +3775,6 @@ int gs_pairing_sum(gs_ctx* c, int k, const void* x, const void* y, void* out) {
       memcpy(&P[((size_t)cell * k + i) * g1], xb + (size_t)i * 2 * g1 + a * g1, g1);
       memcpy(&Q[((size_t)cell * k + i) * g2], yb + (size_t)i * 2 * g2 + b * g2, g2);
     }
-  }
-  if (k == 0) {  // empty sum: four GT identities
-    gs_ctx* cc = c;
-    (void)cc;
   }
   return gs_multi_pairing_batch(c, 4, k, P.data(), Q.data(), out);
 }

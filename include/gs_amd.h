@@ -112,7 +112,8 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  * Unset = planned.  GS_COPY_THREADS (default 4): memcpy workers of the host-pointer entry points; GS_ROCTX=1: load the
  * roctx library for phase markers ("gs.prove", "gs.prove.g1", "gs.verify.miller" ...) even when no profiler mapped it.
  * Diagnostics on stderr: GS_PLAN_TRACE=1 (the verifier's Miller plan per call: mode, budget, tasks per equation, planned
- * cost of each task's lane, waves), GS_PIPE_TRACE=1 (time line of a host-pointer call's staging, uploads and arrivals);
+ * cost of each task's lane, waves; and one line "[plan] table <name> <count> <content hash>" per task table a call uses,
+ * cached or not), GS_PIPE_TRACE=1 (time line of a host-pointer call's staging, uploads and arrivals);
  * GS_PIPE_NO_DIRECT=1 stages registered arrays like pageable ones. */
 int gs_set_option(gs_ctx* ctx, const char* key, int value);
 int gs_sync(gs_ctx* ctx);                         /* hipStreamSynchronize on the context's stream */
