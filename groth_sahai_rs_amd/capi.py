@@ -21,6 +21,7 @@ SYMBOLS = [
     "gs_commit_g1", "gs_commit_g2", "gs_commit_fr_b1", "gs_commit_fr_b2",
     "gs_prove_batch_dev", "gs_prove_batch", "gs_verify_batch_dev", "gs_verify_batch",
     "gs_verify_batch_rlc_dev", "gs_verify_batch_rlc", "gs_gt_finalize",
+    "gs_verify_batch_rlc_locate_dev", "gs_verify_batch_rlc_locate",
     "gs_verify_statements_rlc_dev", "gs_verify_statements_rlc",
     "gs_prove_statement_dev", "gs_prove_statement", "gs_verify_statement_dev", "gs_verify_statement",
     "gs_mat_left_mul_com1", "gs_mat_left_mul_com2", "gs_pairing_sum", "gs_fr_matmul",
@@ -232,7 +233,8 @@ class Engine:
 
     def set_option(self, key, value):
         """Planner override (include/gs_amd.h, gs_set_option): miller_twin, miller_ch, var_tm, var_mo, var_w, red_k, coop_fe, line_tables,
-        overlap.  Results never change, only which kernel shapes run."""
+        overlap; locate_k (0 | 2 | 4 | 8): the arity of verify_batch_rlc_locate's product tree.  Results never change,
+        only which kernel shapes run (locate_k changes which nodes exist, hence info[1] and what can cancel)."""
         self._chk(self.lib.gs_set_option(self.ctx, key.encode(), int(value)))
 
     def set_crs(self, crs):
@@ -460,6 +462,22 @@ class Engine:
                                                _p(ok)))
         return int(ok[0]), acc
 
+    def verify_batch_rlc_locate(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
+        """Batched verifier with fault localisation (host buffers; the arrays and rho of verify_batch_rlc).  Returns
+        (ok[N], info, acc): ok[e] = 0 iff the descent of the kept product tree reached leaf e and it failed, info =
+        [number of zeros in ok, number of node checks], acc = the accumulator pair of verify_batch_rlc."""
+        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
+        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
+        self._check_verify("gs_verify_batch_rlc_locate", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
+        _need("gs_verify_batch_rlc_locate", [("rho", rho, 32 * N)])
+        acc = self._out(2 * self.GT)
+        ok = np.zeros(N, dtype=np.uint8)
+        info = np.zeros(2, dtype=np.uint32)
+        self._chk(self.lib.gs_verify_batch_rlc_locate(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
+                                                      _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho),
+                                                      _p(acc), _p(ok), _p(info)))
+        return ok, info, acc
+
     def _check_statements(self, fn, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc=None,
                           ok=None):
         """Byte lengths of S statements of E equations: S copies of a Statement's (shared) layout with N = E."""
@@ -584,6 +602,18 @@ class Engine:
         self._chk(self.lib.gs_verify_batch_rlc_dev(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
                                                    _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho),
                                                    _p(acc)))
+
+    def verify_batch_rlc_locate_dev(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok, info):
+        """Device form: rho uint64[N*4], acc one accumulator pair, ok N bytes, info 2 x uint32, all on the device
+        (asynchronous)."""
+        self._check_verify("gs_verify_batch_rlc_locate_dev", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
+        _need("gs_verify_batch_rlc_locate_dev", [("rho", rho, 32 * N), ("acc", acc, 2 * self.GT), ("ok", ok, N),
+                                                 ("info", info, 8)])
+        if acc is None or ok is None or info is None:
+            raise GsError(3, "gs_verify_batch_rlc_locate_dev: acc, ok and info are required")
+        self._chk(self.lib.gs_verify_batch_rlc_locate_dev(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B),
+                                                          _p(Gamma), _p(target), _p(xcoms), _p(ycoms), _p(pi),
+                                                          _p(theta), _p(rho), _p(acc), _p(ok), _p(info)))
 
     def verify_statements_rlc_dev(self, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok):
         """Device form: rho uint64[S*E*4], acc S accumulator pairs, ok S bytes, all on the device (asynchronous)."""

@@ -111,6 +111,7 @@ struct gs_ctx {
   int var_mo = 0, var_w = 0;  // outputs per Straus lane (1, 2, 4) and its window width (4, 5); 0 = planned
   int miller_ch = 0, miller_twin = -1;
   int coop_fe = 1;  // 0 never, 1 when one lane per final exponentiation cannot fill the chip, 2 always
+  int locate_k = 0;  // arity of gs_verify_batch_rlc_locate's product tree (2, 4, 8); 0 = planned (8, as gt_product)
   bool line_tables = true;  // pairs whose G2 argument is a CRS element read precomputed Miller lines
   // host-pointer entry points (HostPipe below): pinned staging, a copy stream, memcpy workers, per-array events
   struct HostPipe* pipe = nullptr;  // set while a host-pointer call is enqueuing its kernels
@@ -2156,9 +2157,10 @@ template <class C> struct Impl {
   //   1. C'_ib = rho_0b c_i.0 + rho_1b c_i.1,  Th'_lb = rho_0b theta_l.0 + rho_1b theta_l.1
   //   2. P'_jb = rho_1b A_j + sum_i Gamma_ij C'_ib   (a_j rho_ab W1.a for scalar constants),
   //      PB'_b, U'_kb = rho_0b u_k.0 + rho_1b u_k.1, W1'_b      (Com-shaped: components b = 0, 1)
-  static int verify_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                        const uint64_t* rho, void* acc) {
+  // rlc_front: the pool, both G1 passes and the Miller launch; leaves N * ntask partials, equation-major, in rlc.mpart
+  static int rlc_front(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                       const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                       const uint64_t* rho, void** mpart, int* ntask_out) {
     bool xg = x_is_group(ty), yg = y_is_group(ty);
     int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
     PoolMap pm;
@@ -2251,11 +2253,17 @@ template <class C> struct Impl {
                                  {3, pi, (uint32_t)(kx * Z::COM2)},
                                  {4, target, (uint32_t)Z::G2}});
     const std::vector<MillerTask> mt = plan_miller_single(c, N, pr);
-    const int ntask = (int)mt.size();
+    *ntask_out = (int)mt.size();
+    return miller_single(c, "rlc", N, mt, parr, qarr, mpart);
+  }
+  static int verify_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                        const uint64_t* rho, void* acc) {
     void *mpart, *pt, *tmp;
+    int ntask;
+    RC(rlc_front(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, &mpart, &ntask));
     RC(scratch(c, "rlc.t", (N + 1) * sizeof(GT), &pt));
     RC(scratch(c, "rlc.tmp", (N * ntask / 4 + 8) * sizeof(GT), &tmp));
-    RC(miller_single(c, "rlc", N, mt, parr, qarr, &mpart));
     uint8_t* a = (uint8_t*)acc;
     RC(gt_product(c, N * ntask, (GT*)mpart, (GT*)tmp, a));
     if (ty == GS_PPE) {
@@ -2264,6 +2272,81 @@ template <class C> struct Impl {
     } else {
       RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, (GT*)pt));
       RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)pt, a + Z::GT));
+    }
+    return GS_OK;
+  }
+
+  // The batched verifier with fault localisation.  Same front; the products are a K-ary tree whose
+  // levels are KEPT: level 0 = the N leaves (f_e, t_e), level l = products of runs of K of level l - 1, one node at the
+  // top.  The descent then runs from the root down, one launch per level, each sized for the whole level: the frontier
+  // (failing nodes of the level above, and how many) is device memory, so nothing here waits for the device.
+  //   rlc.lvl.f / rlc.lvl.t   the levels, one after the other (t only for PPE: it is one everywhere else)
+  //   rlc.frontier            u32: counts[0 .. L + 1] (failing nodes per level; [L + 1] = 1, the root's virtual parent),
+  //                           then the lists of levels 1 .. L and the virtual parent's list {0}
+  static int verify_rlc_locate(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                               const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                               const void* theta, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
+    void* mpart;
+    int ntask;
+    RC(rlc_front(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, &mpart, &ntask));
+    const int K = c->locate_k ? c->locate_k : 8;  // planned: the arity of gt_product
+    const bool ppe = ty == GS_PPE;
+    std::vector<size_t> cnt{N}, off{0};
+    while (cnt.back() > 1) {
+      off.push_back(off.back() + cnt.back());
+      cnt.push_back((cnt.back() + K - 1) / K);
+    }
+    const int L = (int)cnt.size() - 1;
+    const size_t nodes = off[L] + 1;
+    void *lf, *lt = nullptr, *fr;
+    RC(scratch(c, "rlc.lvl.f", nodes * sizeof(GT), &lf));
+    if (ppe) RC(scratch(c, "rlc.lvl.t", nodes * sizeof(GT), &lt));
+    const size_t hdr = (size_t)L + 2, fr_words = hdr + (nodes - N) + 1;
+    RC(scratch(c, "rlc.frontier", fr_words * sizeof(uint32_t), &fr));
+    GT *F = (GT*)lf, *T = (GT*)lt;
+    uint32_t* count = (uint32_t*)fr;
+    auto list = [&](int l) { return count + hdr + (l > L ? nodes - N : off[l] - N); };  // l = 1 .. L + 1
+    hipStream_t st = c->cur ? c->cur : c->stream;
+    HIPCHK(c, hipMemsetAsync(fr, 0, fr_words * sizeof(uint32_t), st));
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)(count + L + 1), 1, 1, st));
+    HIPCHK(c, hipMemsetAsync(ok, 1, N, st));
+    HIPCHK(c, hipMemsetAsync(info, 0, 2 * sizeof(uint32_t), st));
+    // ---- the levels
+    RC(launch(c, "k_rlc_leaf", k_rlc_leaf<C>, N, 64, N, ntask, (const GT*)mpart, F));
+    if (ppe) RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, N, 64, N, (const uint8_t*)target, rho, T));
+    for (int l = 1; l <= L; l++) {
+      const size_t half = (cnt[l] + 63) / 64 * 64;
+      RC(launch(c, "k_rlc_tree", k_rlc_tree<C>, ppe ? half + cnt[l] : cnt[l], 64, cnt[l - 1], (const GT*)(F + off[l - 1]),
+                (const GT*)(ppe ? T + off[l - 1] : nullptr), cnt[l], F + off[l], ppe ? T + off[l] : nullptr, K));
+    }
+    uint8_t* a = (uint8_t*)acc;
+    RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)(F + off[L]), a));
+    if (ppe) {
+      RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)(T + off[L]), a + Z::GT));
+    } else {
+      void* one;
+      RC(scratch(c, "rlc.one", sizeof(GT), &one));
+      RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, (GT*)one));
+      RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)one, a + Z::GT));
+    }
+    // ---- the descent: level L is the root under its virtual parent, level 0 the leaves
+    for (int l = L; l >= 0; l--) {
+      LocateLevel lv;
+      lv.fr_in = list(l + 1);
+      lv.cnt_in = count + l + 1;
+      lv.fr_out = l ? list(l) : nullptr;
+      lv.cnt_out = l ? count + l : nullptr;
+      lv.n_child = (uint32_t)cnt[l];
+      lv.fan = l == L ? 1 : K;
+      lv.ok = l ? nullptr : ok;
+      lv.info = info;
+      const size_t items = l == L ? 1 : cnt[l + 1] * (size_t)K, coop_waves = (items + 20) / 21;
+      const GT *Fl = F + off[l], *Tl = ppe ? T + off[l] : nullptr;
+      // one lane per node check once the level's launch fills the chip, 3-lane groups (21 per wave) below that
+      if (c->coop_fe == 2 || (c->coop_fe == 1 && coop_waves <= c->simd_slots))
+        RC(launch(c, "k_rlc_locate.coop", k_rlc_locate_coop<C>, coop_waves * 63, 63, lv, Fl, Tl));
+      else
+        RC(launch(c, "k_rlc_locate", k_rlc_locate<C>, items, 64, lv, Fl, Tl));
     }
     return GS_OK;
   }
@@ -2865,6 +2948,9 @@ int gs_set_option(gs_ctx* c, const char* key, int value) {
   } else if (k == "coop_fe") {
     if (value < 0 || value > 2) return fail(c, GS_ERR_ARG, "coop_fe: 0 never, 1 planned, 2 always");
     c->coop_fe = value;
+  } else if (k == "locate_k") {
+    if (value != 0 && value != 2 && value != 4 && value != 8) return fail(c, GS_ERR_ARG, "locate_k: 0 (planned), 2, 4, 8");
+    c->locate_k = value;
   } else if (k == "dlog_steps") {
     if (value < 0) return fail(c, GS_ERR_ARG, "dlog_steps: 0 (default) or the giant steps per launch");
     c->dlog_steps = value;
@@ -3833,6 +3919,65 @@ int gs_verify_batch_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A
   RC(st.back(hacc.data(), dacc, hacc.size()));
   if (acc) memcpy(acc, hacc.data(), hacc.size());
   if (ok_all) RC(gs_gt_finalize(c, 1, hacc.data(), ok_all));
+  return GS_OK;
+}
+// ---- batched verifier with fault localisation: the product tree is kept and descended from the root ----------------
+int gs_verify_batch_rlc_locate_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                                   const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                                   const void* theta, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
+  RC(check_ctx(c, true));
+  RC(check_shape(c, ty, m, n));
+  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !acc || !ok || !info || N == 0)
+    return fail(c, GS_ERR_ARG, "null pointer or empty batch");
+  if (N >= ((size_t)1 << 32) / 8) return fail(c, GS_ERR_SHAPE, "gs_verify_batch_rlc_locate: node indices are 32-bit");
+  return DISPATCH(c, verify_rlc_locate(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok, info));
+}
+int gs_verify_batch_rlc_locate(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                               const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                               const void* theta, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
+  RC(check_ctx(c, true));
+  RC(check_shape(c, ty, m, n));
+  if (N == 0) return fail(c, GS_ERR_ARG, "empty batch");
+  if (!rho || !ok) return fail(c, GS_ERR_ARG, "null pointer");
+  for (size_t i = 0; i < 4 * N; i++)  // a zero exponent drops its cell equation from every node check above its leaf
+    if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
+  const lay::Layout L(sz_fq(c->curve), ty, N, m, n, false);
+  const void* const h[8] = {A, B, G, target, xcoms, ycoms, pi, theta};
+  static const lay::Array arr[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
+  const size_t acc_bytes = 2 * 12 * sz_fq(c->curve);
+  {  // no output may lie over an input or over another output
+    const void* in_p[9] = {A, B, G, target, xcoms, ycoms, pi, theta, rho};
+    size_t in_n[9];
+    for (int i = 0; i < 8; i++) in_n[i] = L.bytes[arr[i]];
+    in_n[8] = N * 4 * sizeof(uint64_t);
+    const void* out_p[3] = {ok, info, acc};
+    const size_t out_n[3] = {N, 2 * sizeof(uint32_t), acc_bytes};
+    for (int o = 0; o < 3; o++) {
+      if (!out_p[o]) continue;
+      for (int i = 0; i < 9; i++)
+        if (in_p[i] && in_n[i] && ranges_overlap(out_p[o], out_n[o], in_p[i], in_n[i]))
+          return fail(c, GS_ERR_ARG, "gs_verify_batch_rlc_locate: an output overlaps an input");
+      for (int q = 0; q < o; q++)
+        if (out_p[q] && ranges_overlap(out_p[o], out_n[o], out_p[q], out_n[q]))
+          return fail(c, GS_ERR_ARG, "gs_verify_batch_rlc_locate: the outputs overlap each other");
+    }
+  }
+  HostStage st(c);
+  void *d[8], *drho, *dacc, *dok, *dinfo;
+  std::vector<uint8_t> hacc(acc_bytes);
+  uint32_t hinfo[2] = {0, 0};
+  for (int i = 0; i < 8; i++) RC(st.in(h[i], L.bytes[arr[i]], &d[i]));
+  RC(st.in(rho, N * 4 * sizeof(uint64_t), &drho));
+  RC(st.out(hacc.data(), hacc.size(), &dacc));
+  RC(st.out(ok, N, &dok));
+  RC(st.out(hinfo, sizeof hinfo, &dinfo));
+  RC(gs_verify_batch_rlc_locate_dev(c, ty, N, m, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], (const uint64_t*)drho,
+                                    dacc, (uint8_t*)dok, (uint32_t*)dinfo));
+  RC(st.back(hacc.data(), dacc, hacc.size()));
+  RC(st.back(ok, dok, N));
+  RC(st.back(hinfo, dinfo, sizeof hinfo));
+  if (acc) memcpy(acc, hacc.data(), hacc.size());
+  if (info) memcpy(info, hinfo, sizeof hinfo);
   return GS_OK;
 }
 // ---- statement-batched (RLC) verifier: S statements of E equations over shared commitments ----------------------

@@ -1529,12 +1529,15 @@ __global__ void __launch_bounds__(64, GS_WPE) k_gt_prod_seg(size_t S, size_t len
 // One statement: product of its ntask Miller partials (the un-exponentiated accumulator), final exponentiation,
 // comparison with the statement's target product (tprod; null = one).  Writes the verdict and the boundary-form pair
 // (acc[s][0] = Miller product, acc[s][1] = target product) that gs_gt_finalize takes.
-template <class C>
-__device__ __forceinline__ void stmt_product(Fp12<C>& f, Fp12<C>& t, const Fp12<C>* mpart, const Fp12<C>* tprod, size_t s,
-                                             int ntask) {
+template <class C> __device__ __forceinline__ void miller_product(Fp12<C>& f, const Fp12<C>* mpart, size_t s, int ntask) {
   const Fp12<C>* p = mpart + s * (size_t)ntask;
   f = p[0];
   for (int i = 1; i < ntask; i++) f12_mul(f, f, p[i]);
+}
+template <class C>
+__device__ __forceinline__ void stmt_product(Fp12<C>& f, Fp12<C>& t, const Fp12<C>* mpart, const Fp12<C>* tprod, size_t s,
+                                             int ntask) {
+  miller_product(f, mpart, s, ntask);
   if (tprod)
     t = tprod[s];
   else
@@ -1578,6 +1581,119 @@ struct k_stmt_final_coop {
   if (live && j == 0) ok[s] = same ? 1 : 0;
 }
 };
+
+// ---- fault localisation of the batched verifier (gs_verify_batch_rlc_locate): K-ary product tree, kept ----------------
+// Leaf e = (f_e, t_e): f_e the product of equation e's ntask Miller partials, t_e = k_rlc_tpow's power (PPE; one
+// otherwise, not stored).  Node (l, i) = product of nodes (l-1, i K .. i K + K - 1).  All levels live in one buffer per
+// side, level after level.  A node passes iff FE(f) == t; the descent checks the root and every child of a failing node.
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE) k_rlc_leaf(size_t N, int ntask, const Fp12<C>* mpart, Fp12<C>* f0) {
+  size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N) return;
+  Fp12<C> f;
+  miller_product(f, mpart, e, ntask);
+  f0[e] = f;
+}
+// one level up, both sides in one launch: lanes [0, n_out) fold fin, lanes [half, half + n_out) fold tin (tin null: the
+// launch ends at n_out); half = n_out rounded up to whole waves, so no wave straddles the sides
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE) k_rlc_tree(size_t n_in, const Fp12<C>* fin, const Fp12<C>* tin, size_t n_out,
+                                                         Fp12<C>* fout, Fp12<C>* tout, int K) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t half = (n_out + 63) / 64 * 64;
+  const bool ts = g >= half;
+  if (ts) g -= half;
+  if (g >= n_out || (ts && !tin)) return;
+  const Fp12<C>* in = ts ? tin : fin;
+  size_t lo = g * (size_t)K, hi = lo + K < n_in ? lo + K : n_in;
+  Fp12<C> acc = in[lo];
+  for (size_t i = lo + 1; i < hi; i++) f12_mul(acc, acc, in[i]);
+  (ts ? tout : fout)[g] = acc;
+}
+// One level of the descent.  Item g = (failing parent fr_in[g / fan], child g % fan); the child is node
+// fr_in[g / fan] * fan + g % fan of this level if that is < n_child (the last parent of a level may have fewer children).
+// The launch covers the whole level; *cnt_in (device memory) says how much of it there is to do.
+struct LocateLevel {
+  const uint32_t* fr_in;   // failing nodes one level up (order free)
+  const uint32_t* cnt_in;  // how many
+  uint32_t* fr_out;        // failing nodes of this level are appended here ...
+  uint32_t* cnt_out;       // ... and counted here (both unused at level 0)
+  uint32_t n_child;        // nodes of this level
+  int fan;                 // children per parent: K, or 1 for the root under its virtual parent
+  uint8_t* ok;             // level 0 only: ok[e] = 0 for a failing leaf
+  uint32_t* info;          // [0] += failing leaves, [1] += node checks
+};
+// the wave's bookkeeping: one ballot per flag, one atomic per counter and wave (lane 0; every lane of the wave is here)
+__device__ __forceinline__ void locate_commit(const LocateLevel& L, int lane, bool checked, bool bad, uint32_t node) {
+  const unsigned long long mc = __ballot(checked), mb = __ballot(bad);
+  uint32_t base = 0;
+  if (lane == 0) {
+    if (mc) atomicAdd(L.info + 1, (uint32_t)__popcll(mc));
+    if (mb) {
+      if (L.ok)
+        atomicAdd(L.info, (uint32_t)__popcll(mb));
+      else
+        base = atomicAdd(L.cnt_out, (uint32_t)__popcll(mb));
+    }
+  }
+  if (L.ok) {
+    if (bad) L.ok[node] = 0;
+    return;
+  }
+  base = (uint32_t)__shfl((int)base, 0, 64);
+  if (bad) L.fr_out[base + (uint32_t)__popcll(mb & ((1ull << lane) - 1))] = node;
+}
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE) k_rlc_locate(LocateLevel L, const Fp12<C>* F, const Fp12<C>* T) {
+  const int lane = (int)threadIdx.x;
+  const size_t g0 = (size_t)blockIdx.x * blockDim.x, g = g0 + lane;
+  const size_t items = (size_t)*L.cnt_in * (size_t)L.fan;
+  if (g0 >= items) return;  // a whole wave beyond the frontier
+  bool live = g < items;
+  size_t node = 0;
+  if (live) {
+    node = (size_t)L.fr_in[g / L.fan] * (size_t)L.fan + g % L.fan;
+    live = node < L.n_child;
+  }
+  bool bad = false;
+  if (live) {
+    Fp12<C> f = F[node], t, r;
+    if (T)
+      t = T[node];
+    else
+      f12_one(t);
+    final_exp(r, f);
+    bad = !f12_eq(r, t);
+  }
+  locate_commit(L, lane, live, bad, (uint32_t)node);
+}
+// The same with a 3-lane group per item (gs_coop.cuh; blockDim.x == 63: 21 groups per wave).  Idle groups of a live wave
+// shadow child 0 of the first frontier node (it always exists) so that every lane reaches the shuffles.
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE) k_rlc_locate_coop(LocateLevel L, const Fp12<C>* F, const Fp12<C>* T) {
+  const int lane = (int)threadIdx.x, j = lane % 3;
+  const size_t g0 = (size_t)blockIdx.x * 21, g = g0 + lane / 3;
+  const size_t items = (size_t)*L.cnt_in * (size_t)L.fan;
+  if (g0 >= items) return;  // a whole wave beyond the frontier
+  bool live = g < items;
+  size_t node = 0;
+  if (live) {
+    node = (size_t)L.fr_in[g / L.fan] * (size_t)L.fan + g % L.fan;
+    live = node < L.n_child;
+  }
+  if (!live) node = (size_t)L.fr_in[0] * (size_t)L.fan;
+  Fp12<C> f = F[node], t, r;
+  if (T)
+    t = T[node];
+  else
+    f12_one(t);
+  CoopWave xw{lane - j};
+  ExpXCoop<C, CoopWave> ex{j, &xw};
+  final_exp_with(r, f, ex);
+  const bool same = f12_eq(r, t);
+  const bool mine = live && j == 0;
+  locate_commit(L, lane, mine, mine && !same, (uint32_t)node);
+}
 
 // --------------------------------------------------------------------------
 // wire format (gs_wire.cuh): arrays of elements, one lane per element

@@ -345,6 +345,34 @@ def _draw_rho(rng, count):
     return out
 
 
+def verify_batch_locate(equations, com_proofs, crs, rng):
+    """[bool per equation] for INDEPENDENT equations of one type and shape, each with its own CProof (one EquProof),
+    from the batched verifier with fault localisation (gs_verify_batch_rlc_locate): one combined check when the batch is
+    valid, a descent of the kept product tree to the failing proofs when it is not.  True means "lies under a node
+    whose combined check passed" (include/gs_amd.h): each such check errs with probability 2^-64 over rho, which is
+    drawn here from `rng`."""
+    N = len(equations)
+    assert N >= 1 and len(com_proofs) == N
+    ty = equations[0].TYPE
+    kx, ky = equations[0]._kxky()
+    m, n = len(com_proofs[0].xcoms.coms), len(com_proofs[0].ycoms.coms)
+    assert m >= 1 and n >= 1
+    for equ, cp in zip(equations, com_proofs):
+        assert equ.TYPE == ty and len(cp.equ_proofs) == 1 and cp.equ_proofs[0].equ_type == ty
+        assert len(cp.xcoms.coms) == m and len(cp.ycoms.coms) == n
+        equ._check_statement_shape(m, n)
+        assert len(cp.equ_proofs[0].pi) == kx and len(cp.equ_proofs[0].theta) == ky
+    cat = np.concatenate
+    ok, _, _ = crs.engine.verify_batch_rlc_locate(
+        ty, N, m, n, cat([_cat(e.a_consts, 0) for e in equations]), cat([_cat(e.b_consts, 0) for e in equations]),
+        cat([_flat_mat(e.gamma) for e in equations]),
+        cat([np.asarray(e.target, dtype=np.uint64).reshape(-1) for e in equations]),
+        cat([_cat(cp.xcoms.coms, 0) for cp in com_proofs]), cat([_cat(cp.ycoms.coms, 0) for cp in com_proofs]),
+        cat([_cat(cp.equ_proofs[0].pi, 0) for cp in com_proofs]),
+        cat([_cat(cp.equ_proofs[0].theta, 0) for cp in com_proofs]), _draw_rho(rng, 4 * N))
+    return [bool(v) for v in ok]
+
+
 class Statement:
     """`pub type Statement = Vec<dyn Equ>` (statement.rs:109) made usable: a list of equations of ONE type over the same
     variables (statement.rs:24-28: "each equation is defined with respect to the list of variables that span across

@@ -9,6 +9,7 @@
  *                             xcoms/ycoms != NULL src/prover/prove.rs:72-90,175-193,278-296,383-408 (commit_and_prove)
  *   gs_verify_batch        <- src/verifier.rs:23-157       (Verifiable::verify, exact semantics, bool per equation)
  *   gs_verify_batch_rlc    <- (new) batched pairing-product check, one final exponentiation per batch
+ *   gs_verify_batch_rlc_locate <- (new) the same check with the product tree kept and descended: which proofs are bad
  *   gs_rerandomize_batch   <- (new) rerandomization of commitments and proofs without the witness (the same
  *                             algebra as src/prover/prove.rs:92-171,195-274,298-379,409-488 applied to fresh randomness)
  *   gs_mat_left_mul_com1/2 <- src/data_structures.rs:696-742 (Mat::left_mul on Matrix<Com1/Com2>)
@@ -106,6 +107,8 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  *   "dlog_steps"    0 = 2^15 (an estimate) | giant steps one k_dlog launch walks; longer walks are several launches
  *   "dlog_fp_bits"  0 = all 35 | 1 .. 35 fingerprint bits a lookup of gs_dlog_* compares (small values force false hits,
  *                   which the confirmation rejects).  Both are test knobs without an environment twin.
+ *   "locate_k"      0 planned (8, the arity of the batched verifier's own product) | 2, 4, 8 arity of the product tree of
+ *                   gs_verify_batch_rlc_locate[_dev].  A test knob without an environment twin.
  * The same knobs are read ONCE at gs_ctx_create from the environment for experiments without recompiling the caller:
  * GS_MILLER_TWIN, GS_MILLER_CH, GS_VAR_TM, GS_VAR_MO, GS_VAR_W, GS_VAR_W2, GS_RED_K, GS_COOP_FE, GS_LINE_TABLES, GS_OVERLAP,
  * GS_ENDO (same values).
@@ -402,6 +405,51 @@ int gs_verify_batch_rlc_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const
 int gs_verify_batch_rlc(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
                         const void* Gamma, const void* target, const void* xcoms, const void* ycoms, const void* pi,
                         const void* theta, const uint64_t* rho, void* acc_gt, uint8_t* ok_all);
+/* The batched check WITH FAULT LOCALISATION: the same inputs, layouts and accumulator pair as gs_verify_batch_rlc, and
+ * one byte per equation that says where the faults are.  The products of gs_verify_batch_rlc are taken as a K-ary tree
+ * (K = 8, "locate_k") whose levels are KEPT in device memory:
+ *   leaf e            (f_e, t_e): f_e = the product of equation e's Miller partials, t_e = target_e^rho[e][3] for PPE,
+ *                     one otherwise
+ *   node (l, i)       the product of its at most K children (l - 1, i K .. i K + K - 1); the root is the pair acc_gt
+ *   a node PASSES     iff FE(f) == t
+ * and descended: the root is checked; every child of a failing node is checked, down to the leaves (no child is inferred
+ * from its siblings).
+ *   ok[e] = 0         iff leaf e was reached and failed
+ *   ok[e] = 1         iff e lies under some node that passed (the root included).  This is NOT exact verification: a set
+ *                     of faults that cancels inside a passing node is not seen -- nor does gs_verify_batch_rlc see it.
+ *   info[0]           the number of entries with ok == 0
+ *   info[1]           the number of node checks (final exponentiations) of the descent: 1 for the root plus, for every
+ *                     failing internal node, the number of its children.  Both are functions of the inputs and K alone.
+ *   acc_gt            the root pair, byte for byte what gs_verify_batch_rlc_dev writes for the same inputs and options.
+ * RHO CONTRACT: that of gs_verify_batch_rlc above, unchanged (CSPRNG, fresh per call, NON-ZERO, secret until the
+ * verdicts are out, drawn after the batch is fixed; PPE targets are raised to rho without a subgroup check).  Every node
+ * check is a random linear combination over that node's leaves with the SAME exponents, so the soundness error of a
+ * call is at most info[1] * 2^-64.
+ * Cost: a valid batch costs what gs_verify_batch_rlc costs (one node check); b bad proofs cost about b K log_K N more
+ * final exponentiations, against the 4 N of gs_verify_batch.  Advice to callers, from the measurement of DESIGN.md 6.6
+ * (2^16 PPE 4 x 4, one MI355X): there is NO crossover -- the descent is a chain of one-level launches, about 30 ms from one
+ * bad proof to all 65536 of them, for scattered and for contiguous faults alike, so combined check plus descent (186 ..
+ * 189 ms) stays below one exact pass (202 ms) even when every proof is bad, and a valid batch costs the combined check
+ * alone (157.9 against 157.7 ms).  Call this entry instead of gs_verify_batch_rlc followed by gs_verify_batch; call
+ * gs_verify_batch when the verdicts must be exact (see ok[e] = 1 above).
+ * Memory: the stored levels take about 2 N K / (K - 1) GT elements for PPE and half that otherwise, next to the
+ * N * ntask Miller partials gs_verify_batch_rlc keeps anyway.
+ * The _dev entry only enqueues on the context's stream (the frontier of failing nodes and its length stay in device
+ * memory; every level's launch is sized for the whole level); ok[N], info[2] and acc_gt are device pointers, all
+ * required.  The host entry stages like the other host entries, rejects rho == 0 and outputs that overlap an input or
+ * each other (GS_ERR_ARG), and returns when ok, info and acc_gt are back; acc_gt and info may be NULL there.  N == 0 is
+ * GS_ERR_ARG; N >= 2^29 is GS_ERR_SHAPE (node indices and the items of a level's launch are 32-bit).  "endo" 0 is
+ * followed as in gs_verify_batch_rlc; "coop_fe" selects the one-lane or the 3-lane final exponentiation of the node
+ * checks (0 / 2 force, 1 plans per level from the launch size).  The multi-GPU handles (gs_multi_*) have no counterpart.
+ * Kernel profile names: "k_rlc_leaf", "k_rlc_tree" (one launch per level), "k_rlc_locate[.coop]" (one launch per level). */
+int gs_verify_batch_rlc_locate_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                                   const void* Gamma, const void* target, const void* xcoms, const void* ycoms,
+                                   const void* pi, const void* theta, const uint64_t* rho, void* acc_gt,
+                                   uint8_t* ok /* [N] */, uint32_t* info /* [2] */);
+int gs_verify_batch_rlc_locate(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                               const void* Gamma, const void* target, const void* xcoms, const void* ycoms,
+                               const void* pi, const void* theta, const uint64_t* rho, void* acc_gt,
+                               uint8_t* ok /* [N] */, uint32_t* info /* [2] */);
 /* Batched verifier for STATEMENTS: S statements of one type and shape, each E equations over ONE set of commitments
  * (the arrays of statement s are exactly what gs_verify_statement takes, at offset s: A[S][E][n], B[S][E][m],
  * Gamma[S][E][m][n], target[S][E], xcoms[S][m], ycoms[S][n], pi[S][E][kx], theta[S][E][ky]; rho[S][E][4] u64).

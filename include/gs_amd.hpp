@@ -1014,41 +1014,18 @@ inline CRS deserialize_crs(const Bytes& b, bool compressed, int curve = GS_CURVE
   return CRS(r.coms<Com1>(u), r.coms<Com2>(v), G1Affine{r.get(g1)}, G2Affine{r.get(g2)}, GT{r.get(gt)}, curve, device);
 }
 
-// ---- several GPUs of one node (gs_ctx_create_multi): a batch of N same-shaped equations, proved / verified in
-// contiguous blocks, one per device.  The reference has no batch type (Statement = Vec<dyn Equ> is unused there), so
-// the batch is given as vectors of equations and per-equation witnesses; everything else follows Equation<>.
-struct MultiCtx {
-  gs_multi* h = nullptr;
-  size_t sz[6] = {0, 0, 0, 0, 0, 0};
-  MultiCtx(int curve, const std::vector<int>& devices) {
-    if (gs_sizes(curve, sz) != GS_OK) throw std::runtime_error("bad curve id");
-    if (gs_ctx_create_multi(curve, devices.data(), (int)devices.size(), &h) != GS_OK)
-      throw std::runtime_error("gs_ctx_create_multi failed (no usable GPU; there is no CPU fallback)");
-  }
-  ~MultiCtx() { gs_multi_destroy(h); }
-  MultiCtx(const MultiCtx&) = delete;
-  MultiCtx& operator=(const MultiCtx&) = delete;
-  void chk(int rc) const {
-    if (rc == GS_ERR_SHAPE) throw Panic(gs_multi_last_error(h));
-    if (rc != GS_OK) throw std::runtime_error(std::string("gs_amd error: ") + gs_multi_last_error(h));
-  }
-  void set_crs(const CRS& crs) {
-    Bytes flat = cat(crs.u), t = cat(crs.v);
-    flat.insert(flat.end(), t.begin(), t.end());
-    flat.insert(flat.end(), crs.g1_gen.v.begin(), crs.g1_gen.v.end());
-    flat.insert(flat.end(), crs.g2_gen.v.begin(), crs.g2_gen.v.end());
-    flat.insert(flat.end(), crs.gt_gen.v.begin(), crs.gt_gen.v.end());
-    assert_eq(flat.size(), sz[5], "CRS size");
-    chk(gs_multi_set_crs(h, flat.data()));
-  }
-  // verify N proofs of N equations of ONE type and shape (m x n); ok[i] as Verifiable::verify of equation i
-  template <class Equ> std::vector<bool> verify_batch(const std::vector<Equ>& equs, const std::vector<CProof>& proofs) {
+// the eight verifier arrays of N proofs of N equations of ONE type and shape (m x n), packed equation after equation
+// with every length the C ABI will index checked first (what MultiCtx::verify_batch and verify_batch_locate hand over)
+namespace detail {
+struct BatchArrays {
+  size_t m = 0, n = 0;
+  Bytes A, B, G, tg, xc, yc, pi, th;
+  template <class Equ> BatchArrays(const size_t* sz, const std::vector<Equ>& equs, const std::vector<CProof>& proofs) {
     assert_eq(equs.size(), proofs.size(), "equs.len() == proofs.len()");
     size_t N = equs.size();
-    if (N == 0) return {};
-    size_t m = proofs[0].xcoms.coms.size(), n = proofs[0].ycoms.coms.size();
+    if (N == 0) throw Panic("index out of bounds: empty batch");
+    m = proofs[0].xcoms.coms.size(), n = proofs[0].ycoms.coms.size();
     if (m == 0 || n == 0) throw Panic("index out of bounds: empty commitment list");
-    Bytes A, B, G, tg, xc, yc, pi, th;
     auto app = [](Bytes& d, const Bytes& s) { d.insert(d.end(), s.begin(), s.end()); };
     const EquType ty = equs[0].get_type();
     const bool xs = ty == EquType::MultiScalarG2 || ty == EquType::Quadratic, ys = ty == EquType::MultiScalarG1 || ty == EquType::Quadratic;
@@ -1084,9 +1061,67 @@ struct MultiCtx {
     assert_eq(A.size(), N * n * sx, "a_consts bytes");
     assert_eq(B.size(), N * m * sy, "b_consts bytes");
     assert_eq(tg.size(), N * tsz, "target bytes");
+  }
+};
+}  // namespace detail
+
+// (new) N INDEPENDENT equations of one type and shape, each with its own CProof, through the batched verifier with fault
+// localisation (gs_verify_batch_rlc_locate): one combined pairing check when every proof is good, a descent of the
+// kept product tree to the failing proofs when not.  ok[i] = true means "equation i lies under a node whose combined
+// check passed" -- each such check errs with probability 2^-64 over rho, drawn here from `rng` (rng.u64() when it has
+// one, else the low 64 bits of rng.fr(); non-zero): the rho contract of gs_amd.h.
+template <class Equ, class Rng>
+std::vector<bool> verify_batch_locate(const std::vector<Equ>& equs, const std::vector<CProof>& proofs, const CRS& crs, Rng& rng) {
+  const Ctx& cx = *crs.ctx;
+  const detail::BatchArrays a(cx.sz, equs, proofs);
+  const size_t N = equs.size();
+  std::vector<uint64_t> rho(4 * N);
+  for (uint64_t& r : rho) {
+    r = 0;
+    while (r == 0) r = detail::draw_u64(rng, 0);
+  }
+  std::vector<uint8_t> ok(N, 0);
+  cx.chk(gs_verify_batch_rlc_locate(cx.c, (int)equs[0].get_type(), N, (int)a.m, (int)a.n, a.A.data(), a.B.data(), a.G.data(),
+                                    a.tg.data(), a.xc.data(), a.yc.data(), a.pi.data(), a.th.data(), rho.data(), nullptr,
+                                    ok.data(), nullptr));
+  return std::vector<bool>(ok.begin(), ok.end());
+}
+
+// ---- several GPUs of one node (gs_ctx_create_multi): a batch of N same-shaped equations, proved / verified in
+// contiguous blocks, one per device.  The reference has no batch type (Statement = Vec<dyn Equ> is unused there), so
+// the batch is given as vectors of equations and per-equation witnesses; everything else follows Equation<>.
+struct MultiCtx {
+  gs_multi* h = nullptr;
+  size_t sz[6] = {0, 0, 0, 0, 0, 0};
+  MultiCtx(int curve, const std::vector<int>& devices) {
+    if (gs_sizes(curve, sz) != GS_OK) throw std::runtime_error("bad curve id");
+    if (gs_ctx_create_multi(curve, devices.data(), (int)devices.size(), &h) != GS_OK)
+      throw std::runtime_error("gs_ctx_create_multi failed (no usable GPU; there is no CPU fallback)");
+  }
+  ~MultiCtx() { gs_multi_destroy(h); }
+  MultiCtx(const MultiCtx&) = delete;
+  MultiCtx& operator=(const MultiCtx&) = delete;
+  void chk(int rc) const {
+    if (rc == GS_ERR_SHAPE) throw Panic(gs_multi_last_error(h));
+    if (rc != GS_OK) throw std::runtime_error(std::string("gs_amd error: ") + gs_multi_last_error(h));
+  }
+  void set_crs(const CRS& crs) {
+    Bytes flat = cat(crs.u), t = cat(crs.v);
+    flat.insert(flat.end(), t.begin(), t.end());
+    flat.insert(flat.end(), crs.g1_gen.v.begin(), crs.g1_gen.v.end());
+    flat.insert(flat.end(), crs.g2_gen.v.begin(), crs.g2_gen.v.end());
+    flat.insert(flat.end(), crs.gt_gen.v.begin(), crs.gt_gen.v.end());
+    assert_eq(flat.size(), sz[5], "CRS size");
+    chk(gs_multi_set_crs(h, flat.data()));
+  }
+  // verify N proofs of N equations of ONE type and shape (m x n); ok[i] as Verifiable::verify of equation i
+  template <class Equ> std::vector<bool> verify_batch(const std::vector<Equ>& equs, const std::vector<CProof>& proofs) {
+    size_t N = equs.size();
+    if (N == 0 && proofs.empty()) return {};
+    const detail::BatchArrays a(sz, equs, proofs);
     std::vector<uint8_t> ok(N, 0);
-    chk(gs_multi_verify_batch(h, (int)equs[0].get_type(), N, (int)m, (int)n, A.data(), B.data(), G.data(), tg.data(),
-                              xc.data(), yc.data(), pi.data(), th.data(), ok.data()));
+    chk(gs_multi_verify_batch(h, (int)equs[0].get_type(), N, (int)a.m, (int)a.n, a.A.data(), a.B.data(), a.G.data(),
+                              a.tg.data(), a.xc.data(), a.yc.data(), a.pi.data(), a.th.data(), ok.data()));
     return std::vector<bool>(ok.begin(), ok.end());
   }
 };
