@@ -2644,18 +2644,23 @@ static int left_mul_impl(gs_ctx* c, int rows, int k, const void* lhs, const void
   RC(scratch(c, "lm.pool", (size_t)pm.total * sizeof(S), &pool));
   RC(launch_seg<k_prep_verify<C>>(c, "k_prep_verify", 1, 64, (size_t)1, rows, k, (const S*)dl, (const S*)nullptr,
             (const S*)nullptr, (const S*)nullptr, pm, (S*)pool));
+  // Planned: one term per lane (k_var).  The forced Straus shapes are honoured so that the lanes can be driven with
+  // chosen bases and scalars: var_tm > 1 groups the k terms of a component (all rows run over the same 2 k bases, so
+  // share_tables gives var_mo outputs per lane), var_tab = 1 (G1) puts them on shared window tables of the 2 k bases.
+  // endo = 0 keeps the plain lanes.
   SidePlan sp;
-  int slot = 0;
-  for (int i = 0; i < rows; i++) {
-    int b[2], e[2];
-    for (int a = 0; a < 2; a++) {
-      b[a] = slot;
-      for (int j = 0; j < k; j++) sp.var.push_back(mkvar(i * k + j, 0, 2 * j + a, slot++));
-      e[a] = slot;
-    }
-    sp.red.push_back(mkred(b[0], e[0], b[1], e[1], 0, i));
+  if (c->endo && c->var_tab == 1 && std::is_same<F, Fq<C>>::value) {
+    sp.tm = 8;
+    sp.tab_bases = 2 * k;
+  } else if (c->endo && c->var_tm > 1) {
+    sp.tm = c->var_tm;
   }
-  sp.nslots = slot;
+  ComOutputs outp{sp};
+  outp.add(rows, 0, 0, [&](int i, int a, ComOutputs& o) {
+    std::vector<VarTask> terms;
+    for (int j = 0; j < k; j++) terms.push_back(mkvar(i * k + j, 0, 2 * j + a, 0));
+    o.terms(terms);
+  });
   RC((run_side<C, F>(c, ".lm", 1, sp, arr_tab({{0, dc, 0}}), (const S*)pool, pm.total, (const Aff<F>*)nullptr,
                      out_tab(dout, 0))));
   return st.back(out, dout, (size_t)rows * com);

@@ -93,7 +93,13 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  *                   the commitment components shared by all outputs (8-bit windows; what large arities use)
  *   "var_w2"       -1 planned | 0 | 1 the G1 Straus lanes in the kernels built for TWO waves per SIMD (256 registers: the
  *                   register-only G1 point operations leave room); planned when a launch puts two waves on every SIMD
- *   "endo"          1 (default) GLV / psi-GLS scalar multiplications: r-torsion points only | 0 every variable-base scalar
+ *                   gs_mat_left_mul_com1/2 plan one term per lane ("k_var.lm") and FOLLOW the forced Straus shapes: with
+ *                   "var_tm" > 1 the k terms of every output component run in balanced groups of at most var_tm terms
+ *                   under "var_w", "var_mo" (all rows run over the same 2 k bases), "var_w2" and "var_ws_lanes"
+ *                   ("k_var_multi<4|8>[w5][x<mo>].lm"); "var_tab" = 1 puts com1 on shared window tables of the 2 k
+ *                   column components ("k_tab_build.lm", "k_var_tab8.lm"; com2 ignores it: the shared tables have no G2
+ *                   caller).  That is how the tests drive those lanes with chosen bases and scalars.
+ *   "endo"         1 (default) GLV / psi-GLS scalar multiplications: r-torsion points only | 0 every variable-base scalar
  *                   multiplication is a plain signed-window double-and-add lane ("k_var.plain", "k_smul_batch.plain"):
  *                   defined on ANY curve point, like the reference's Com::scalar_mul (data_structures.rs:336-342), at
  *                   ~2.5x the variable-base work.  For callers that cannot vouch for subgroup membership and do not want

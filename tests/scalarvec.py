@@ -14,7 +14,8 @@ oracle/gs_oracle.py and oracle/gs_ref.c.  The constants are read from csrc/gs_pa
   stream_digits(...)        signed width-W digits of every stream, plain_digits(k) those of recode_w4
   selfcheck(cname)          the classes are really in the table; returns the reached correction counts / sign patterns
 
-Classes: universal, window16, exponent, and per curve bls_g1 / bls_g2 / bn_g1 / bn_g2 (DESIGN.md 4.1 has the prose)."""
+Classes: universal, window16, exponent, and per curve bls_g1 / bls_g2 / bls_w8 / bn_g1 / bn_g2 (DESIGN.md 4.1 has the
+prose)."""
 import functools
 import os
 import random
@@ -343,6 +344,15 @@ def _bls_g2(m):
     return out
 
 
+def _bls_w8(m):
+    """8-bit windows (k_var_tab8): the largest digit, +127, in the two upper base-|x| streams of G2, which no other class
+    puts there twice -- a lone 0x7f in window 0 and in window 1 of d2 and of d3"""
+    x = m.xabs
+    out = [("g2_w8_d%d=%x" % (j, v), v * x ** j) for j in (2, 3) for v in (0x7F, 0x7F00)]
+    assert all(k < m.r for _, k in out)
+    return out
+
+
 def _bn(m, group):
     r = m.r
     G, GS, B, gw = m.lat[group]
@@ -376,7 +386,7 @@ def _build(cname):
     if m.bn:
         parts += [("bn_g1", _bn(m, 1)), ("bn_g2", _bn(m, 2))]
     else:
-        parts += [("bls_g1", _bls_g1(m)), ("bls_g2", _bls_g2(m))]
+        parts += [("bls_g1", _bls_g1(m)), ("bls_g2", _bls_g2(m)), ("bls_w8", _bls_w8(m))]
     by_value, order, names = {}, [], {}
     for cls, lst in parts:
         for name, k in lst:
@@ -426,12 +436,13 @@ def stream_bound(cname, group, s):
 
 def selfcheck(cname):
     """Every class is there, every reached correction count / sign pattern has its scalars, and every stream sees the
-    most negative digit and a carry past its top window, at both widths.  Returns the reached sets."""
+    most negative digit and a carry past its top window, at the widths 4, 5 and 8; at W = 8 the largest digit as well,
+    twice.  Returns the reached sets."""
     m = model(cname)
     tab = table(cname)
     ks = [c.k for c in tab]
     assert len(tab) < 700 and len(set(ks)) == len(ks) and all(0 <= k < m.r for k in ks)
-    classes = ["universal", "window16", "exponent"] + (["bn_g1", "bn_g2"] if m.bn else ["bls_g1", "bls_g2"])
+    classes = ["universal", "window16", "exponent"] + (["bn_g1", "bn_g2"] if m.bn else ["bls_g1", "bls_g2", "bls_w8"])
     for cls in classes:
         assert scalars(cname, cls), cls
     out = {}
@@ -477,7 +488,7 @@ def selfcheck(cname):
         out[group] = reached(cname, group)
         # digits: -2^(W-1) in every stream; a carry past the top window of the value in every stream; the spare digit
         # itself wherever the stream's range lets a magnitude reach it
-        for W in (4, 5):
+        for W in (4, 5, 8):
             ND = nd_of(NL, W)
             for s in range(NS):
                 streams = [recode(d.mags[s], NL, W) for d in decs]
@@ -487,6 +498,8 @@ def selfcheck(cname):
                 can = stream_bound(cname, group, s) >= spare_threshold(ND, W)
                 assert any(dg[-1] == 1 for dg in streams) == can, (group, W, s, can)
                 assert all(dg[-1] in (0, 1) for dg in streams)
+                if W == 8:  # (the widths 4 and 5 get their largest digit from the repeated nibbles and quintets)
+                    assert sum(1 for dg in streams if 127 in dg) >= 2, (group, s)
     # the plain path: digit -8, the carry chain into the top nibble, and the proof that the spare digit stays 0
     nd = (m.nbits + 3) // 4 + 1
     assert spare_threshold(nd, 4) > m.r - 1

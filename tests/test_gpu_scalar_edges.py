@@ -164,8 +164,8 @@ EDGE = ["r-1", "one", "nibbles_8", "nibbles_7", "(r+1)/2", "quints_10000"]
 def test_mat_left_mul_table(cid, cname, group, k):
     """Rows of k consecutive table scalars, shifted cyclically: every scalar visits every term position.  Behind them
     the rows (s, r - s) on (P, P) and (s, s) on (P, -P), which must give the identity.  gs_mat_left_mul plans one term
-    per lane (k_var.lm) whatever var_tm / var_w / var_mo say -- the Straus lanes are reached through prove and verify
-    below -- so the forcings that take effect here are the planner's own choice and endo = 0 (k_var.plain.lm)."""
+    per lane (k_var.lm); here it runs as planned and with endo = 0 (k_var.plain.lm).  Under a forced var_tm / var_w /
+    var_mo it takes the Straus lanes: tests/test_gpu_straus_edges.py."""
     import gs_ref_py as ref
 
     K = ctx(cid, cname)

@@ -1,6 +1,6 @@
 """Scalar decomposition and digit recoding on the CPU twin (no GPU): the named scalars of tests/scalarvec.py and 20 000
 seeded random ones through endo_digits<C, W> (Barrett division by lambda / |x| on BLS12-381, lattice rounding on BN254,
-recode_w_limbs at W = 4 and 5) and recode_w4, and the whole table through the scalar multiplications and the Straus MSM
+recode_w_limbs at W = 4, 5 and 8 -- the last the windows of k_var_tab8) and recode_w4, and the whole table through the scalar multiplications and the Straus MSM
 built on them, against the big-integer oracle.
 
 What a digit stream must satisfy comes from plain integer arithmetic (range, recombination, sum +-k_j eig^j = k mod r);
@@ -50,7 +50,7 @@ def test_table_holds_its_classes(cname):
     assert S.selfcheck(cname) == REACHED[cname]
 
 
-@pytest.mark.parametrize("W", [4, 5])
+@pytest.mark.parametrize("W", [4, 5, 8])
 @pytest.mark.parametrize("group", [1, 2])
 @pytest.mark.parametrize("cname", CURVES)
 def test_endo_digit_streams(twin, cname, group, W):  # noqa: F811

@@ -168,8 +168,12 @@ template <class C> struct Twin {
     return ND;
   }
   static int digit_streams(int group, int w, int n, const uint32_t* ks, int8_t* dg, uint8_t* sgn) {
-    if (group == 1) return w == 5 ? endo_digits_n<F1, 5>(n, ks, dg, sgn) : endo_digits_n<F1, 4>(n, ks, dg, sgn);
-    return w == 5 ? endo_digits_n<F2, 5>(n, ks, dg, sgn) : endo_digits_n<F2, 4>(n, ks, dg, sgn);
+    // (w = 8: the windows of k_var_tab8's shared base tables)
+    if (group == 1)
+      return w == 8 ? endo_digits_n<F1, 8>(n, ks, dg, sgn)
+                    : w == 5 ? endo_digits_n<F1, 5>(n, ks, dg, sgn) : endo_digits_n<F1, 4>(n, ks, dg, sgn);
+    return w == 8 ? endo_digits_n<F2, 8>(n, ks, dg, sgn)
+                  : w == 5 ? endo_digits_n<F2, 5>(n, ks, dg, sgn) : endo_digits_n<F2, 4>(n, ks, dg, sgn);
   }
   // recode_w4 on the whole scalar (the plain path, jac_smul): n x ND digits.  Returns ND.
   static int recode_plain(int n, const uint32_t* ks, int8_t* dg) {
