@@ -449,61 +449,56 @@ class Engine:
                                                _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(ok)))
         return ok
 
+    def _rlc(self, fn, ty, S, N, m, n, arrays, rho, **outs):
+        """The batched (RLC) verifiers, host and _dev forms: byte lengths, missing outputs, the call.  arrays: A ..
+        theta as verify_batch takes them; S: statements of N = E equations each over shared commitments (None: one
+        unshared batch of N); outs: the entry's outputs in the order of its C signature.  A host form's missing output
+        is allocated here, a _dev form's is refused.  Returns outs."""
+        dev, stmt = fn.endswith("_dev"), S is not None
+        if not dev:
+            rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
+            arrays = [_u8(a) for a in arrays]
+        if stmt and (S < 1 or N < 1):
+            raise GsError(3, "%s: S and E must be >= 1" % fn)
+        if not (0 <= ty <= 3) or m < 1 or n < 1:
+            raise GsError(1, "%s: bad equation type or empty variable list" % fn)
+        k = S if stmt else 1  # combined checks: copies of the layout, accumulator pairs
+        one = self._sizes(ty, N, m, n, stmt)
+        want = dict(rho=32 * k * N, acc=k * 2 * self.GT, ok=S if stmt else N, ok_all=1, info=8)
+        keys = ("A", "B", "Gamma", "target", "xcoms", "ycoms", "pi", "theta")
+        _need(fn, [(key, a, k * one[key]) for key, a in zip(keys, arrays)] +
+              [(key, a, want[key]) for key, a in [("rho", rho)] + list(outs.items())])
+        for key, a in outs.items():
+            if a is None and dev:
+                raise GsError(3, "%s: %s is required" % (fn, key))
+            if a is None:
+                outs[key] = np.zeros(2, dtype=np.uint32) if key == "info" else self._out(want[key])
+        count = [ctypes.c_size_t(S), ctypes.c_size_t(N)] if stmt else [ctypes.c_size_t(N)]
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, *count, m, n,
+                                        *[_p(a) for a in list(arrays) + [rho] + list(outs.values())]))
+        return outs
+
     def verify_batch_rlc(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
         """Batched verifier (host buffers).  rho: uint64[N*4].  Returns (ok_all, acc_pair_bytes)."""
-        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
-        self._check_verify("gs_verify_batch_rlc", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
-        _need("gs_verify_batch_rlc", [("rho", rho, 32 * N)])
-        acc = self._out(2 * self.GT)
-        ok = np.zeros(1, dtype=np.uint8)
-        self._chk(self.lib.gs_verify_batch_rlc(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
-                                               _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho), _p(acc),
-                                               _p(ok)))
-        return int(ok[0]), acc
+        o = self._rlc("gs_verify_batch_rlc", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
+                      acc=None, ok_all=None)
+        return int(o["ok_all"][0]), o["acc"]
 
     def verify_batch_rlc_locate(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
         """Batched verifier with fault localisation (host buffers; the arrays and rho of verify_batch_rlc).  Returns
         (ok[N], info, acc): ok[e] = 0 iff the descent of the kept product tree reached leaf e and it failed, info =
         [number of zeros in ok, number of node checks], acc = the accumulator pair of verify_batch_rlc."""
-        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
-        self._check_verify("gs_verify_batch_rlc_locate", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
-        _need("gs_verify_batch_rlc_locate", [("rho", rho, 32 * N)])
-        acc = self._out(2 * self.GT)
-        ok = np.zeros(N, dtype=np.uint8)
-        info = np.zeros(2, dtype=np.uint32)
-        self._chk(self.lib.gs_verify_batch_rlc_locate(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
-                                                      _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho),
-                                                      _p(acc), _p(ok), _p(info)))
-        return ok, info, acc
-
-    def _check_statements(self, fn, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc=None,
-                          ok=None):
-        """Byte lengths of S statements of E equations: S copies of a Statement's (shared) layout with N = E."""
-        if S < 1 or E < 1:
-            raise GsError(3, "%s: S and E must be >= 1" % fn)
-        if not (0 <= ty <= 3) or m < 1 or n < 1:
-            raise GsError(1, "%s: bad equation type or empty variable list" % fn)
-        one = self._sizes(ty, E, m, n, True)
-        arrays = dict(A=A, B=B, Gamma=Gamma, target=target, xcoms=xcoms, ycoms=ycoms, pi=pi, theta=theta)
-        _need(fn, [(k, a, S * one[k]) for k, a in arrays.items()] +
-              [("rho", rho, S * E * 32), ("acc", acc, S * 2 * self.GT), ("ok", ok, S)])
+        o = self._rlc("gs_verify_batch_rlc_locate", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta),
+                      rho, acc=None, ok=None, info=None)
+        return o["ok"], o["info"], o["acc"]
 
     def verify_statements_rlc(self, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
         """Batched verifier for S statements of E equations each over shared commitments (host buffers; the arrays
         of statement s are what verify_statement takes, at offset s).  rho: uint64[S*E*4], non-zero, from a CSPRNG
         (the rho contract of gs_amd.h).  Returns (ok[S], acc[S][2] GT bytes)."""
-        rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
-        A, B, Gamma, target, xcoms, ycoms, pi, theta = map(_u8, (A, B, Gamma, target, xcoms, ycoms, pi, theta))
-        self._check_statements("gs_verify_statements_rlc", ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi,
-                               theta, rho)
-        acc = self._out(S * 2 * self.GT)
-        ok = np.zeros(S, dtype=np.uint8)
-        self._chk(self.lib.gs_verify_statements_rlc(self.ctx, ty, ctypes.c_size_t(S), ctypes.c_size_t(E), m, n, _p(A),
-                                                    _p(B), _p(Gamma), _p(target), _p(xcoms), _p(ycoms), _p(pi),
-                                                    _p(theta), _p(rho), _p(acc), _p(ok)))
-        return ok, acc.reshape(S, 2, self.GT)
+        o = self._rlc("gs_verify_statements_rlc", ty, S, E, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
+                      acc=None, ok=None)
+        return o["ok"], o["acc"].reshape(S, 2, self.GT)
 
     def gt_finalize_dev(self, accs_dev, count):
         """the same with `count` pairs in device memory (torch tensor)."""
@@ -597,33 +592,19 @@ class Engine:
                                                _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(ok)))
 
     def verify_batch_rlc_dev(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc):
-        self._check_verify("gs_verify_batch_rlc_dev", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
-        _need("gs_verify_batch_rlc_dev", [("rho", rho, 32 * N), ("acc", acc, 2 * self.GT)])
-        self._chk(self.lib.gs_verify_batch_rlc_dev(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B), _p(Gamma),
-                                                   _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(rho),
-                                                   _p(acc)))
+        self._rlc("gs_verify_batch_rlc_dev", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
+                  acc=acc)
 
     def verify_batch_rlc_locate_dev(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok, info):
         """Device form: rho uint64[N*4], acc one accumulator pair, ok N bytes, info 2 x uint32, all on the device
         (asynchronous)."""
-        self._check_verify("gs_verify_batch_rlc_locate_dev", ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta)
-        _need("gs_verify_batch_rlc_locate_dev", [("rho", rho, 32 * N), ("acc", acc, 2 * self.GT), ("ok", ok, N),
-                                                 ("info", info, 8)])
-        if acc is None or ok is None or info is None:
-            raise GsError(3, "gs_verify_batch_rlc_locate_dev: acc, ok and info are required")
-        self._chk(self.lib.gs_verify_batch_rlc_locate_dev(self.ctx, ty, ctypes.c_size_t(N), m, n, _p(A), _p(B),
-                                                          _p(Gamma), _p(target), _p(xcoms), _p(ycoms), _p(pi),
-                                                          _p(theta), _p(rho), _p(acc), _p(ok), _p(info)))
+        self._rlc("gs_verify_batch_rlc_locate_dev", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta),
+                  rho, acc=acc, ok=ok, info=info)
 
     def verify_statements_rlc_dev(self, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok):
         """Device form: rho uint64[S*E*4], acc S accumulator pairs, ok S bytes, all on the device (asynchronous)."""
-        self._check_statements("gs_verify_statements_rlc_dev", ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi,
-                               theta, rho, acc, ok)
-        if acc is None or ok is None:
-            raise GsError(3, "gs_verify_statements_rlc_dev: acc and ok are required")
-        self._chk(self.lib.gs_verify_statements_rlc_dev(self.ctx, ty, ctypes.c_size_t(S), ctypes.c_size_t(E), m, n,
-                                                        _p(A), _p(B), _p(Gamma), _p(target), _p(xcoms), _p(ycoms),
-                                                        _p(pi), _p(theta), _p(rho), _p(acc), _p(ok)))
+        self._rlc("gs_verify_statements_rlc_dev", ty, S, E, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
+                  acc=acc, ok=ok)
 
     def g_mul_batch_dev(self, group, n, points, broadcast, scalars, out):
         fn = self.lib.gs_g1_mul_batch_dev if group == 1 else self.lib.gs_g2_mul_batch_dev

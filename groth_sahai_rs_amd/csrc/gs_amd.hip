@@ -2606,6 +2606,24 @@ struct HostStage {  // host<->device staging for the un-suffixed entry points
     return GS_OK;
   }
 };
+// The plain host form of a checked call: stage the inputs in, give every output a slot, run(d) on the device pointers
+// (d[] holds the inputs' first, then the outputs', in the order listed), copy the outputs back.
+struct HostBuf {
+  const void* h;
+  size_t bytes;
+};
+template <class Run>
+static int staged_call(gs_ctx* c, std::initializer_list<HostBuf> ins, std::initializer_list<HostBuf> outs, Run run) {
+  HostStage st(c);
+  void* d[8];
+  int k = 0;
+  for (const HostBuf& b : ins) RC(st.in(b.h, b.bytes, &d[k++]));
+  for (const HostBuf& b : outs) RC(st.out(const_cast<void*>(b.h), b.bytes, &d[k++]));
+  RC(run(d));
+  k = (int)ins.size();
+  for (const HostBuf& b : outs) RC(st.back(const_cast<void*>(b.h), d[k++], b.bytes));
+  return GS_OK;
+}
 
 // Forget the binding key.  The digit streams on the device are the only copy the context keeps.
 static void clear_extraction_key(gs_ctx* c) {
@@ -2708,26 +2726,18 @@ template <class C> struct WireImpl {
   template <class F> static int enc_pts(gs_ctx* c, size_t n, int compressed, const void* pts, uint8_t* out) {
     if (n == 0) return GS_OK;
     size_t pb = AFFB(C, F), wb = wire_point_bytes<C, F>(compressed != 0);
-    HostStage st(c);
-    void *din, *dout;
-    RC(st.in(pts, n * pb, &din));
-    RC(st.out(out, n * wb, &dout));
-    RC(launch(c, "k_wire_enc_pts", k_wire_enc_pts<C, F>, n, 64, n, (const uint8_t*)din, compressed, (uint8_t*)dout));
-    return st.back(out, dout, n * wb);
+    return staged_call(c, {{pts, n * pb}}, {{out, n * wb}}, [&](void** d) {
+      return launch(c, "k_wire_enc_pts", k_wire_enc_pts<C, F>, n, 64, n, (const uint8_t*)d[0], compressed, (uint8_t*)d[1]);
+    });
   }
   template <class F>
   static int dec_pts(gs_ctx* c, size_t n, int compressed, int validate, const uint8_t* in, void* pts, uint8_t* ok) {
     if (n == 0) return GS_OK;
     size_t pb = AFFB(C, F), wb = wire_point_bytes<C, F>(compressed != 0);
-    HostStage st(c);
-    void *din, *dout, *dok;
-    RC(st.in(in, n * wb, &din));
-    RC(st.out(pts, n * pb, &dout));
-    RC(st.out(ok, n, &dok));
-    RC(launch(c, "k_wire_dec_pts", k_wire_dec_pts<C, F>, n, 64, n, (const uint8_t*)din, compressed, validate,
-              (uint8_t*)dout, (uint8_t*)dok));
-    RC(st.back(pts, dout, n * pb));
-    return st.back(ok, dok, n);
+    return staged_call(c, {{in, n * wb}}, {{pts, n * pb}, {ok, n}}, [&](void** d) {
+      return launch(c, "k_wire_dec_pts", k_wire_dec_pts<C, F>, n, 64, n, (const uint8_t*)d[0], compressed, validate,
+                    (uint8_t*)d[1], (uint8_t*)d[2]);
+    });
   }
   // on-curve + r-torsion check of in-memory points (device pointers)
   template <class F> static int validate_pts_dev(gs_ctx* c, size_t n, const void* pts, uint8_t* ok) {
@@ -3155,24 +3165,28 @@ COMMIT_DEV(gs_commit_g2_dev, Fp2, true, tab16_g2, ".cg2")
 COMMIT_DEV(gs_commit_fr_b1_dev, Fq, false, tab16_g1, ".cg1")
 COMMIT_DEV(gs_commit_fr_b2_dev, Fp2, false, tab16_g2, ".cg2")
 
-#define COMMIT_HOST(NAME, DEVNAME, VSZ, KC, OSZ)                           \
-  int NAME(gs_ctx* c, size_t n, const void* v, const void* r, void* out) { \
-    RC(check_ctx(c, true));                                                \
-    if (n == 0) return GS_OK;                                              \
-    if (!v || !r || !out) return GS_ERR_ARG;                               \
-    size_t fq = sz_fq(c->curve);                                           \
-    HostStage st(c);                                                       \
-    void *dv, *dr, *dout;                                                  \
-    RC(st.in(v, n * (VSZ), &dv));                                          \
-    RC(st.in(r, n * (KC)*SZ_FR, &dr));                                     \
-    RC(st.out(out, n * (OSZ), &dout));                                     \
-    RC(DEVNAME(c, n, dv, dr, dout));                                       \
-    return st.back(out, dout, n * (OSZ));                                  \
-  }
-COMMIT_HOST(gs_commit_g1, gs_commit_g1_dev, 2 * fq, 2, 4 * fq)
-COMMIT_HOST(gs_commit_g2, gs_commit_g2_dev, 4 * fq, 2, 8 * fq)
-COMMIT_HOST(gs_commit_fr_b1, gs_commit_fr_b1_dev, SZ_FR, 1, 4 * fq)
-COMMIT_HOST(gs_commit_fr_b2, gs_commit_fr_b2_dev, SZ_FR, 1, 8 * fq)
+// vq: Fq per committed value (0: an Fr scalar), kc: scalars of randomness per value, oq: Fq per commitment
+static int commit_host(gs_ctx* c, int (*dev)(gs_ctx*, size_t, const void*, const void*, void*), size_t vq, size_t kc,
+                       size_t oq, size_t n, const void* v, const void* r, void* out) {
+  RC(check_ctx(c, true));
+  if (n == 0) return GS_OK;
+  if (!v || !r || !out) return GS_ERR_ARG;
+  const size_t fq = sz_fq(c->curve);
+  return staged_call(c, {{v, n * (vq ? vq * fq : SZ_FR)}, {r, n * kc * SZ_FR}}, {{out, n * oq * fq}},
+                     [&](void** d) { return dev(c, n, d[0], d[1], d[2]); });
+}
+int gs_commit_g1(gs_ctx* c, size_t n, const void* v, const void* r, void* out) {
+  return commit_host(c, gs_commit_g1_dev, 2, 2, 4, n, v, r, out);
+}
+int gs_commit_g2(gs_ctx* c, size_t n, const void* v, const void* r, void* out) {
+  return commit_host(c, gs_commit_g2_dev, 4, 2, 8, n, v, r, out);
+}
+int gs_commit_fr_b1(gs_ctx* c, size_t n, const void* v, const void* r, void* out) {
+  return commit_host(c, gs_commit_fr_b1_dev, 0, 1, 4, n, v, r, out);
+}
+int gs_commit_fr_b2(gs_ctx* c, size_t n, const void* v, const void* r, void* out) {
+  return commit_host(c, gs_commit_fr_b2_dev, 0, 1, 8, n, v, r, out);
+}
 
 // ---- prove / verify / rerandomize: shared plumbing ------------------------------------------------------------
 static int check_shape(gs_ctx* c, int ty, int m, int n) {
@@ -3597,22 +3611,17 @@ int gs_extract_g2_dev(gs_ctx* c, size_t n, const void* coms, void* out) {
   return WIRE_DISPATCH((extract_impl<Bls12_381, Fp2<Bls12_381>>(c, "k_extract.g2", 2, n, coms, out)),
                        (extract_impl<Bn254, Fp2<Bn254>>(c, "k_extract.g2", 2, n, coms, out)));
 }
-#define EXTRACT_HOST(NAME, DEVNAME, PT)                             \
-  int NAME(gs_ctx* c, size_t n, const void* coms, void* out) {      \
-    RC(check_ctx(c, true));                                         \
-    if (!c->have_xkey) return fail(c, GS_ERR_ARG, "gs_set_extraction_key has not been called"); \
-    if (n == 0) return GS_OK;                                       \
-    if (!coms || !out) return fail(c, GS_ERR_ARG, "null pointer"); \
-    size_t pt = (PT) * sz_fq(c->curve);                             \
-    HostStage st(c);                                                \
-    void *dc, *dout;                                                \
-    RC(st.in(coms, n * 2 * pt, &dc));                               \
-    RC(st.out(out, n * pt, &dout));                                 \
-    RC(DEVNAME(c, n, dc, dout));                                    \
-    return st.back(out, dout, n * pt);                              \
-  }
-EXTRACT_HOST(gs_extract_g1, gs_extract_g1_dev, 2)
-EXTRACT_HOST(gs_extract_g2, gs_extract_g2_dev, 4)
+static int extract_host(gs_ctx* c, bool g2, size_t n, const void* coms, void* out) {
+  RC(check_ctx(c, true));
+  if (!c->have_xkey) return fail(c, GS_ERR_ARG, "gs_set_extraction_key has not been called");
+  if (n == 0) return GS_OK;
+  if (!coms || !out) return fail(c, GS_ERR_ARG, "null pointer");
+  const size_t pt = (g2 ? 4 : 2) * sz_fq(c->curve);
+  return staged_call(c, {{coms, n * 2 * pt}}, {{out, n * pt}},
+                     [&](void** d) { return (g2 ? gs_extract_g2_dev : gs_extract_g1_dev)(c, n, d[0], d[1]); });
+}
+int gs_extract_g1(gs_ctx* c, size_t n, const void* coms, void* out) { return extract_host(c, false, n, coms, out); }
+int gs_extract_g2(gs_ctx* c, size_t n, const void* coms, void* out) { return extract_host(c, true, n, coms, out); }
 
 // ---- bounded discrete logarithms: baby-step giant-step (csrc/gs_kernels.cuh: k_dlog_table, k_dlog) ------------------
 }  // extern "C"
@@ -3730,14 +3739,9 @@ static int dlog_host(gs_ctx* c, const char* fn, int gi, bool coms, size_t n, con
   const size_t in_bytes = (coms ? 2 : 1) * (gi ? 4 : 2) * sz_fq(c->curve);
   RC(dlog_check(c, fn, gi, n, in, in_bytes, bits, out, found));
   if (n == 0) return GS_OK;
-  HostStage st(c);
-  void *din, *dout, *dfound;
-  RC(st.in(in, n * in_bytes, &din));
-  RC(st.out(out, n * SZ_FR, &dout));
-  RC(st.out(found, n, &dfound));
-  RC(coms ? extract_scalar_dev(c, fn, gi, n, din, bits, dout, dfound) : dlog_dev(c, fn, gi, n, din, bits, dout, dfound));
-  RC(st.back(out, dout, n * SZ_FR));
-  return st.back(found, dfound, n);
+  return staged_call(c, {{in, n * in_bytes}}, {{out, n * SZ_FR}, {found, n}}, [&](void** d) {
+    return (coms ? extract_scalar_dev : dlog_dev)(c, fn, gi, n, d[0], bits, d[1], d[2]);
+  });
 }
 // k P for n points of G1 (FT = Fq) or G2 (FT = Fp2), `grp` = ".g1" / ".g2"
 template <template <class> class FT>
@@ -3805,13 +3809,9 @@ int gs_g2_mul_batch_dev(gs_ctx* c, size_t n, const void* p, int bc, const void* 
 static int mul_batch_host(gs_ctx* c, bool g2, size_t n, const void* p, int bc, const void* k, void* out) {
   RC(check_ctx(c, false));
   const size_t pt = (g2 ? 4 : 2) * sz_fq(c->curve);  // boundary bytes of one point
-  HostStage st(c);
-  void *dp, *dk, *dout;
-  RC(st.in(p, (bc ? 1 : n) * pt, &dp));
-  RC(st.in(k, n * SZ_FR, &dk));
-  RC(st.out(out, n * pt, &dout));
-  RC(g2 ? gs_g2_mul_batch_dev(c, n, dp, bc, dk, dout) : gs_g1_mul_batch_dev(c, n, dp, bc, dk, dout));
-  return st.back(out, dout, n * pt);
+  return staged_call(c, {{p, (bc ? 1 : n) * pt}, {k, n * SZ_FR}}, {{out, n * pt}}, [&](void** d) {
+    return (g2 ? gs_g2_mul_batch_dev : gs_g1_mul_batch_dev)(c, n, d[0], bc, d[1], d[2]);
+  });
 }
 int gs_g1_mul_batch(gs_ctx* c, size_t n, const void* p, int bc, const void* k, void* out) {
   return mul_batch_host(c, false, n, p, bc, k, out);
@@ -3832,14 +3832,9 @@ int gs_multi_pairing_batch_dev(gs_ctx* c, size_t n, int k, const void* p, const 
 }
 int gs_multi_pairing_batch(gs_ctx* c, size_t n, int k, const void* p, const void* q, void* out) {
   RC(check_ctx(c, false));
-  size_t fq = sz_fq(c->curve);
-  HostStage st(c);
-  void *dp, *dq, *dout;
-  RC(st.in(p, n * k * 2 * fq, &dp));
-  RC(st.in(q, n * k * 4 * fq, &dq));
-  RC(st.out(out, n * 12 * fq, &dout));
-  RC(gs_multi_pairing_batch_dev(c, n, k, dp, dq, dout));
-  return st.back(out, dout, n * 12 * fq);
+  const size_t fq = sz_fq(c->curve);
+  return staged_call(c, {{p, n * k * 2 * fq}, {q, n * k * 4 * fq}}, {{out, n * 12 * fq}},
+                     [&](void** d) { return gs_multi_pairing_batch_dev(c, n, k, d[0], d[1], d[2]); });
 }
 
 int gs_gt_pow_batch_dev(gs_ctx* c, size_t n, const void* base, const void* k, void* out) {
@@ -3892,145 +3887,151 @@ int gs_fr_matmul(gs_ctx* c, int rows, int inner, int cols, const void* lhs, cons
                        fr_matmul_impl<Bn254>(c, rows, inner, cols, lhs, rhs, out));
 }
 
-// ---- batched (RLC) verifier ---------------------------------------------------------
+// ---- batched (RLC) verifiers: one combined check per batch, the same with fault localisation, one per Statement -----
+// All three move the verifier's eight inputs, the exponents rho and up to three outputs.  rlc_arrays states a call's
+// arrays ONCE; the checks of the six entry points and the staging of the three host forms walk that list.
+enum RlcVariant { RLC_PLAIN, RLC_LOCATE, RLC_STMT };
+enum { RLC_RHO = 8, RLC_ACC, RLC_OK, RLC_INFO, RLC_MAX };
+struct RlcCall {
+  RlcVariant v;
+  int ty;
+  size_t S, N;  // RLC_STMT: S statements of N = E equations each over shared commitments; otherwise S = 1
+  int m, n;
+  // A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok (not RLC_PLAIN), info (RLC_LOCATE): host pointers at the
+  // un-suffixed entry points, device pointers at the _dev ones and inside
+  const void* p[RLC_MAX];
+  void* out(int i) const { return const_cast<void*>(p[i]); }
+};
+struct RlcArr {
+  const char* name;
+  const void* p;
+  size_t bytes;
+  int flags;  // ARR_IN / ARR_OUT; ARR_OPT: may be NULL in the host form (a _dev form requires every array)
+};
+// a[i] describes k.p[i]; returns how many the variant has
+static int rlc_arrays(const gs_ctx* c, const RlcCall& k, RlcArr* a) {
+  static const lay::Array in[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
+  const size_t fq = sz_fq(c->curve);
+  const lay::Layout L(fq, k.ty, k.N, k.m, k.n, k.v == RLC_STMT);  // one statement = the shared layout with N = E
+  int na = 0;
+  for (; na < 8; na++) a[na] = {lay::kArrayName[in[na]], k.p[na], k.S * L.bytes[in[na]], ARR_IN};
+  a[na++] = {"rho", k.p[RLC_RHO], 4 * k.S * k.N * sizeof(uint64_t), ARR_IN};        // four exponents per equation
+  a[na++] = {"acc", k.p[RLC_ACC], k.S * 2 * 12 * fq, ARR_OUT | ARR_OPT};            // one GT pair per combined check
+  if (k.v != RLC_PLAIN) a[na++] = {"ok", k.p[RLC_OK], k.v == RLC_STMT ? k.S : k.N, ARR_OUT};
+  if (k.v == RLC_LOCATE) a[na++] = {"info", k.p[RLC_INFO], 2 * sizeof(uint32_t), ARR_OUT | ARR_OPT};
+  return na;
+}
+// everything the six entry points refuse; fills a[] / *na for the caller
+static int rlc_check(gs_ctx* c, const RlcCall& k, bool host, RlcArr* a, int* na) {
+  RC(check_ctx(c, true));
+  RC(check_shape(c, k.ty, k.m, k.n));
+  if (k.S == 0 || k.N == 0)
+    return fail(c, GS_ERR_ARG, k.v == RLC_STMT ? "empty batch: S and E must be >= 1" : "empty batch");
+  // what the plan cannot index is refused
+  if (k.v == RLC_LOCATE && k.N >= ((size_t)1 << 32) / 8)
+    return fail(c, GS_ERR_SHAPE, "gs_verify_batch_rlc_locate: node indices are 32-bit");
+  if (k.v == RLC_STMT) {  // arrays strided per STATEMENT in 32-bit bytes, 32-bit task tables and pool offsets
+    const size_t E = k.N, lim = (size_t)1 << 32;
+    const int m = k.m, n = k.n;
+    const lay::Layout L(sz_fq(c->curve), k.ty, E, m, n, true);
+    if (E > ((size_t)1 << 20) || L.bytes[lay::A] >= lim || L.bytes[lay::B] >= lim || L.bytes[lay::TARGET] >= lim ||
+        L.bytes[lay::PI] >= lim || L.bytes[lay::THETA] >= lim || L.bytes[lay::XCOMS] >= lim ||
+        L.bytes[lay::YCOMS] >= lim || E * (size_t)(4 + 4 * (m + n)) + 4 * (size_t)m * n * 4 >= ((size_t)1 << 28))
+      return fail(c, GS_ERR_SHAPE, "statement too large for the task tables (E x shape)");
+  }
+  *na = rlc_arrays(c, k, a);
+  for (int i = 0; i < *na; i++)
+    if (!a[i].p && !(host && (a[i].flags & ARR_OPT)))
+      return fail(c, GS_ERR_ARG, (std::string("null pointer: ") + a[i].name).c_str());
+  if (!host) return GS_OK;  // device pointers: nothing to read, and whether they overlap is the caller's business
+  const uint64_t* rho = (const uint64_t*)k.p[RLC_RHO];
+  for (size_t i = 0; i < 4 * k.S * k.N; i++)  // a zero exponent drops its cell equation from every check it is part of
+    if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
+  if (k.v != RLC_LOCATE) return GS_OK;
+  for (int o = 0; o < *na; o++) {  // no output may lie over an input or over another output
+    if (!(a[o].flags & ARR_OUT) || !a[o].p) continue;
+    for (int i = 0; i < o; i++)
+      if (a[i].p && ranges_overlap(a[o].p, a[o].bytes, a[i].p, a[i].bytes))
+        return fail(c, GS_ERR_ARG, a[i].flags & ARR_OUT ? "gs_verify_batch_rlc_locate: the outputs overlap each other"
+                                                        : "gs_verify_batch_rlc_locate: an output overlaps an input");
+  }
+  return GS_OK;
+}
+// the kernels of a checked call (device pointers)
+static int rlc_run(gs_ctx* c, const RlcCall& k) {
+  const void* const* p = k.p;
+  const uint64_t* rho = (const uint64_t*)p[RLC_RHO];
+  uint8_t* ok = (uint8_t*)k.out(RLC_OK);
+  switch (k.v) {
+    case RLC_PLAIN:
+      return DISPATCH(c, verify_rlc(c, k.ty, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], rho,
+                                    k.out(RLC_ACC)));
+    case RLC_LOCATE:
+      return DISPATCH(c, verify_rlc_locate(c, k.ty, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], rho,
+                                           k.out(RLC_ACC), ok, (uint32_t*)k.out(RLC_INFO)));
+    case RLC_STMT:
+      return DISPATCH(c, verify_stmt_rlc(c, k.ty, k.S, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7],
+                                         rho, k.out(RLC_ACC), ok));
+  }
+  return GS_ERR_ARG;
+}
+// Any of the six: device pointers run as they are; host pointers are staged in, run and the outputs copied back.
+// ok_all (gs_verify_batch_rlc only; may be NULL): gs_gt_finalize on the returned pair.
+static int rlc_call(gs_ctx* c, const RlcCall& k, bool host, uint8_t* ok_all = nullptr) {
+  RlcArr a[RLC_MAX];
+  int na;
+  RC(rlc_check(c, k, host, a, &na));
+  if (!host) return rlc_run(c, k);
+  std::vector<uint8_t> spare[RLC_MAX];  // an optional output the caller left out is still written: it lands here
+  for (int i = 0; i < na; i++)
+    if (!a[i].p) {
+      spare[i].resize(a[i].bytes);
+      a[i].p = spare[i].data();
+    }
+  HostStage st(c);
+  RlcCall d = k;
+  for (int i = 0; i < na; i++) {
+    void* dp;
+    RC(a[i].flags & ARR_OUT ? st.out(const_cast<void*>(a[i].p), a[i].bytes, &dp) : st.in(a[i].p, a[i].bytes, &dp));
+    d.p[i] = dp;
+  }
+  RC(rlc_run(c, d));
+  for (int i = 0; i < na; i++)
+    if (a[i].flags & ARR_OUT) RC(st.back(const_cast<void*>(a[i].p), d.p[i], a[i].bytes));
+  if (ok_all) RC(gs_gt_finalize(c, 1, a[RLC_ACC].p, ok_all));
+  return GS_OK;
+}
 int gs_verify_batch_rlc_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                             const void* target, const void* xcoms, const void* ycoms, const void* pi,
                             const void* theta, const uint64_t* rho, void* acc) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !acc || N == 0)
-    return fail(c, GS_ERR_ARG, "null pointer or empty batch");
-  return DISPATCH(c, verify_rlc(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, acc));
+  return rlc_call(c, {RLC_PLAIN, ty, 1, N, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc}}, false);
 }
 int gs_verify_batch_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                         const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
                         const uint64_t* rho, void* acc, uint8_t* ok_all) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (N == 0) return fail(c, GS_ERR_ARG, "empty batch");
-  if (!rho) return fail(c, GS_ERR_ARG, "null pointer");
-  for (size_t i = 0; i < 4 * N; i++)  // a zero exponent drops its cell equation from the combined check
-    if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
-  HostStage st(c);
-  const lay::Layout L(sz_fq(c->curve), ty, N, m, n, false);
-  const void* const h[8] = {A, B, G, target, xcoms, ycoms, pi, theta};
-  static const lay::Array arr[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
-  void *d[8], *drho, *dacc;
-  std::vector<uint8_t> hacc(2 * 12 * sz_fq(c->curve));
-  for (int i = 0; i < 8; i++) RC(st.in(h[i], L.bytes[arr[i]], &d[i]));
-  RC(st.in(rho, N * 4 * sizeof(uint64_t), &drho));
-  RC(st.out(hacc.data(), hacc.size(), &dacc));
-  RC(gs_verify_batch_rlc_dev(c, ty, N, m, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], (const uint64_t*)drho, dacc));
-  RC(st.back(hacc.data(), dacc, hacc.size()));
-  if (acc) memcpy(acc, hacc.data(), hacc.size());
-  if (ok_all) RC(gs_gt_finalize(c, 1, hacc.data(), ok_all));
-  return GS_OK;
+  return rlc_call(c, {RLC_PLAIN, ty, 1, N, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc}}, true, ok_all);
 }
 // ---- batched verifier with fault localisation: the product tree is kept and descended from the root ----------------
 int gs_verify_batch_rlc_locate_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                                    const void* target, const void* xcoms, const void* ycoms, const void* pi,
                                    const void* theta, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !acc || !ok || !info || N == 0)
-    return fail(c, GS_ERR_ARG, "null pointer or empty batch");
-  if (N >= ((size_t)1 << 32) / 8) return fail(c, GS_ERR_SHAPE, "gs_verify_batch_rlc_locate: node indices are 32-bit");
-  return DISPATCH(c, verify_rlc_locate(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok, info));
+  return rlc_call(c, {RLC_LOCATE, ty, 1, N, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok, info}}, false);
 }
 int gs_verify_batch_rlc_locate(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                                const void* target, const void* xcoms, const void* ycoms, const void* pi,
                                const void* theta, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (N == 0) return fail(c, GS_ERR_ARG, "empty batch");
-  if (!rho || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  for (size_t i = 0; i < 4 * N; i++)  // a zero exponent drops its cell equation from every node check above its leaf
-    if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
-  const lay::Layout L(sz_fq(c->curve), ty, N, m, n, false);
-  const void* const h[8] = {A, B, G, target, xcoms, ycoms, pi, theta};
-  static const lay::Array arr[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
-  const size_t acc_bytes = 2 * 12 * sz_fq(c->curve);
-  {  // no output may lie over an input or over another output
-    const void* in_p[9] = {A, B, G, target, xcoms, ycoms, pi, theta, rho};
-    size_t in_n[9];
-    for (int i = 0; i < 8; i++) in_n[i] = L.bytes[arr[i]];
-    in_n[8] = N * 4 * sizeof(uint64_t);
-    const void* out_p[3] = {ok, info, acc};
-    const size_t out_n[3] = {N, 2 * sizeof(uint32_t), acc_bytes};
-    for (int o = 0; o < 3; o++) {
-      if (!out_p[o]) continue;
-      for (int i = 0; i < 9; i++)
-        if (in_p[i] && in_n[i] && ranges_overlap(out_p[o], out_n[o], in_p[i], in_n[i]))
-          return fail(c, GS_ERR_ARG, "gs_verify_batch_rlc_locate: an output overlaps an input");
-      for (int q = 0; q < o; q++)
-        if (out_p[q] && ranges_overlap(out_p[o], out_n[o], out_p[q], out_n[q]))
-          return fail(c, GS_ERR_ARG, "gs_verify_batch_rlc_locate: the outputs overlap each other");
-    }
-  }
-  HostStage st(c);
-  void *d[8], *drho, *dacc, *dok, *dinfo;
-  std::vector<uint8_t> hacc(acc_bytes);
-  uint32_t hinfo[2] = {0, 0};
-  for (int i = 0; i < 8; i++) RC(st.in(h[i], L.bytes[arr[i]], &d[i]));
-  RC(st.in(rho, N * 4 * sizeof(uint64_t), &drho));
-  RC(st.out(hacc.data(), hacc.size(), &dacc));
-  RC(st.out(ok, N, &dok));
-  RC(st.out(hinfo, sizeof hinfo, &dinfo));
-  RC(gs_verify_batch_rlc_locate_dev(c, ty, N, m, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], (const uint64_t*)drho,
-                                    dacc, (uint8_t*)dok, (uint32_t*)dinfo));
-  RC(st.back(hacc.data(), dacc, hacc.size()));
-  RC(st.back(ok, dok, N));
-  RC(st.back(hinfo, dinfo, sizeof hinfo));
-  if (acc) memcpy(acc, hacc.data(), hacc.size());
-  if (info) memcpy(info, hinfo, sizeof hinfo);
-  return GS_OK;
+  return rlc_call(c, {RLC_LOCATE, ty, 1, N, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok, info}}, true);
 }
-// ---- statement-batched (RLC) verifier: S statements of E equations over shared commitments ----------------------
-// what the plan cannot index is refused: the engine's arrays are strided per STATEMENT in 32-bit bytes, its task
-// tables and pool offsets are 32-bit
-static int check_stmt_rlc(gs_ctx* c, int ty, size_t S, size_t E, int m, int n) {
-  RC(check_ctx(c, true));
-  RC(check_shape(c, ty, m, n));
-  if (S == 0 || E == 0) return fail(c, GS_ERR_ARG, "empty batch: S and E must be >= 1");
-  const lay::Layout L(sz_fq(c->curve), ty, E, m, n, true);  // one statement = the shared layout with N = E
-  const size_t lim = (size_t)1 << 32;
-  if (E > ((size_t)1 << 20) || L.bytes[lay::A] >= lim || L.bytes[lay::B] >= lim || L.bytes[lay::TARGET] >= lim ||
-      L.bytes[lay::PI] >= lim || L.bytes[lay::THETA] >= lim || L.bytes[lay::XCOMS] >= lim || L.bytes[lay::YCOMS] >= lim ||
-      E * (size_t)(4 + 4 * (m + n)) + 4 * (size_t)m * n * 4 >= ((size_t)1 << 28))
-    return fail(c, GS_ERR_SHAPE, "statement too large for the task tables (E x shape)");
-  return GS_OK;
-}
+// statement-batched: S statements of E equations over shared commitments
 int gs_verify_statements_rlc_dev(gs_ctx* c, int ty, size_t S, size_t E, int m, int n, const void* A, const void* B,
                                  const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
                                  const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
-  RC(check_stmt_rlc(c, ty, S, E, m, n));
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !acc || !ok)
-    return fail(c, GS_ERR_ARG, "null pointer");
-  return DISPATCH(c, verify_stmt_rlc(c, ty, S, E, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok));
+  return rlc_call(c, {RLC_STMT, ty, S, E, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok}}, false);
 }
 int gs_verify_statements_rlc(gs_ctx* c, int ty, size_t S, size_t E, int m, int n, const void* A, const void* B,
                              const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
                              const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
-  RC(check_stmt_rlc(c, ty, S, E, m, n));
-  if (!A || !B || !G || !target || !xcoms || !ycoms || !pi || !theta || !rho || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  for (size_t i = 0; i < 4 * S * E; i++)  // a zero exponent drops its cell equation from the combined check
-    if (rho[i] == 0) return fail(c, GS_ERR_ARG, "rho must be non-zero (see the rho contract in gs_amd.h)");
-  HostStage st(c);
-  const lay::Layout L(sz_fq(c->curve), ty, E, m, n, true);
-  const void* const h[8] = {A, B, G, target, xcoms, ycoms, pi, theta};
-  static const lay::Array arr[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
-  void *d[8], *drho, *dacc, *dok;
-  std::vector<uint8_t> hacc(S * 2 * 12 * sz_fq(c->curve));
-  for (int i = 0; i < 8; i++) RC(st.in(h[i], S * L.bytes[arr[i]], &d[i]));
-  RC(st.in(rho, S * E * 4 * sizeof(uint64_t), &drho));
-  RC(st.out(hacc.data(), hacc.size(), &dacc));
-  RC(st.out(ok, S, &dok));
-  RC(gs_verify_statements_rlc_dev(c, ty, S, E, m, n, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], (const uint64_t*)drho,
-                                  dacc, (uint8_t*)dok));
-  RC(st.back(hacc.data(), dacc, hacc.size()));
-  RC(st.back(ok, dok, S));
-  if (acc) memcpy(acc, hacc.data(), hacc.size());
-  return GS_OK;
+  return rlc_call(c, {RLC_STMT, ty, S, E, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok}}, true);
 }
 int gs_gt_finalize_dev(gs_ctx* c, size_t count, const void* accs_dev, uint8_t* ok) {
   RC(check_ctx(c, false));
@@ -4094,13 +4095,9 @@ int gs_validate_points(gs_ctx* c, int group, size_t n, const void* pts, uint8_t*
   if (group != 1 && group != 2) return fail(c, GS_ERR_ARG, "group: 1 (G1) or 2 (G2)");
   if (n == 0) return GS_OK;
   if (!pts || !ok) return fail(c, GS_ERR_ARG, "null pointer");
-  size_t pb = (group == 1 ? 2 : 4) * sz_fq(c->curve);
-  HostStage st(c);
-  void *din, *dok;
-  RC(st.in(pts, n * pb, &din));
-  RC(st.out(ok, n, &dok));
-  RC(gs_validate_points_dev(c, group, n, din, (uint8_t*)dok));
-  return st.back(ok, dok, n);
+  const size_t pb = (group == 1 ? 2 : 4) * sz_fq(c->curve);
+  return staged_call(c, {{pts, n * pb}}, {{ok, n}},
+                     [&](void** d) { return gs_validate_points_dev(c, group, n, d[0], (uint8_t*)d[1]); });
 }
 
 int gs_wire_encode_fr(gs_ctx* c, size_t n, const void* fr, uint8_t* out) {

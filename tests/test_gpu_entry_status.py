@@ -2,10 +2,12 @@
 return before any array is used: empty batches, bad shapes, unknown types, a context without a CRS and a null pointer
 at every required position.  Raw lib.* calls, as test_status_codes_and_empty_batches in test_gpu_parity.py.
 
-No call here reaches a kernel: every one has either N = 0, a bad shape or type, no CRS, or exactly one required
-pointer nulled.  The non-null pointer is a 64 KiB buffer (numpy for the host entries, a device tensor for the _dev
-ones), larger than any array of the N = 1, m = n = 1 shapes used, so the one entry that copies its arrays up before
-it looks at them (gs_verify_batch_rlc, which also reads rho) stays inside valid memory."""
+No call here reaches a kernel: every one has either N = 0, a bad shape or type, no CRS, exactly one required
+pointer nulled, or (once) an output laid over an input.  Every argument points at its own 4 KiB slice of a 64 KiB
+buffer (numpy for the host entries, a device tensor for the _dev ones): the largest array of the N = 1, m = n = 1
+shapes used is pi with 768 bytes, so no two arguments overlap and the locate host form's overlap refusal cannot answer
+in place of the null check.  No host entry stages an array before it has checked every pointer, but the host forms
+of the batched (RLC) verifiers read rho while checking, so the buffers stay valid memory and non-zero."""
 import ctypes
 
 import numpy as np
@@ -29,9 +31,14 @@ for _sfx in ("", "_dev"):
         ENTRIES["gs_prove_%s%s" % (_kind, _sfx)] = (PROVE, OPTIONAL_COMS, OK)
         ENTRIES["gs_verify_%s%s" % (_kind, _sfx)] = (VERIFY, (), OK)
         ENTRIES["gs_rerandomize_%s%s" % (_kind, _sfx)] = (RERAND, (), OK)
-# the batched verifier refuses an empty batch; the host form's acc and ok_all may be NULL
+# the batched verifiers refuse an empty batch; a _dev form requires every array, the host forms may leave out acc,
+# ok_all and info
 ENTRIES["gs_verify_batch_rlc_dev"] = (VERIFY[:8] + ("rho", "acc"), (), ARG)
 ENTRIES["gs_verify_batch_rlc"] = (VERIFY[:8] + ("rho", "acc", "ok_all"), ("acc", "ok_all"), ARG)
+ENTRIES["gs_verify_batch_rlc_locate_dev"] = (VERIFY[:8] + ("rho", "acc", "ok", "info"), (), ARG)
+ENTRIES["gs_verify_batch_rlc_locate"] = (VERIFY[:8] + ("rho", "acc", "ok", "info"), ("acc", "info"), ARG)
+ENTRIES["gs_verify_statements_rlc_dev"] = (VERIFY[:8] + ("rho", "acc", "ok"), (), ARG)
+ENTRIES["gs_verify_statements_rlc"] = (VERIFY[:8] + ("rho", "acc", "ok"), ("acc",), ARG)
 MIXED = {"gs_prove_mixed": PROVE, "gs_prove_mixed_dev": PROVE, "gs_verify_mixed": VERIFY, "gs_verify_mixed_dev": VERIFY}
 
 
@@ -62,8 +69,17 @@ def _buf(env, name):
     return env["dev"] if name.endswith("_dev") else env["host"]
 
 
+def _slices(env, name, count):
+    """one pointer per argument, 4 KiB apart"""
+    base = _buf(env, name).value
+    assert count * 4096 <= 1 << 16
+    return [ctypes.c_void_p(base + 4096 * i) for i in range(count)]
+
+
 def _call(env, name, ty, N, m, n, ptrs, ctx=None):
-    return getattr(env["e"].lib, name)(ctx or env["e"].ctx, ty, ctypes.c_size_t(N), m, n, *ptrs)
+    """the statements pair takes (S, E) where the others take N: N = 1 is S = E = 1, a tuple is (S, E) itself"""
+    counts = (N if isinstance(N, tuple) else (N, N)) if "statements" in name else (N,)
+    return getattr(env["e"].lib, name)(ctx or env["e"].ctx, ty, *[ctypes.c_size_t(v) for v in counts], m, n, *ptrs)
 
 
 def _err(env):
@@ -73,16 +89,16 @@ def _err(env):
 @pytest.mark.parametrize("name", sorted(ENTRIES))
 def test_entry_status(env, name):
     args, optional, empty_rc = ENTRIES[name]
-    p = _buf(env, name)
-    full = [p] * len(args)
-    # N = 0 with every pointer NULL
-    assert _call(env, name, 0, 0, 1, 1, [Z] * len(args)) == empty_rc
+    full = _slices(env, name, len(args))
+    # N = 0 (S = 0 or E = 0) with every pointer NULL
+    for empty in ((0, 1), (1, 0)) if "statements" in name else (0,):
+        assert _call(env, name, 0, empty, 1, 1, [Z] * len(args)) == empty_rc, empty
     # empty variable lists (the reference panics, prove.rs:106-113)
     for m, n in ((0, 1), (1, 0), (-1, 2)):
         assert _call(env, name, 0, 1, m, n, full) == SHAPE, (m, n)
     # optional pointers: nulling them does not turn a shape error into an argument error
     if optional:
-        assert _call(env, name, 0, 1, 0, 1, [Z if a in optional else p for a in args]) == SHAPE
+        assert _call(env, name, 0, 1, 0, 1, [Z if a in optional else p for a, p in zip(args, full)]) == SHAPE
     # unknown equation type
     assert _call(env, name, 7, 1, 1, 1, full) == ARG
     # no CRS
@@ -96,6 +112,16 @@ def test_entry_status(env, name):
         for ty in (0, 3):
             assert _call(env, name, ty, 1, 1, 1, ptrs) == ARG, (a, ty)
             assert b"null pointer" in _err(env), (a, ty)
+
+
+def test_locate_host_refuses_acc_over_target(env):
+    """The one host form that refuses overlapping arrays (the C ABI with real data: test_gpu_locate.py)."""
+    name = "gs_verify_batch_rlc_locate"
+    args = ENTRIES[name][0]
+    ptrs = _slices(env, name, len(args))
+    ptrs[args.index("acc")] = ptrs[args.index("target")]
+    assert _call(env, name, 0, 1, 1, 1, ptrs) == ARG
+    assert b"overlaps" in _err(env)
 
 
 def _parts(name, specs):
