@@ -23,6 +23,7 @@ SYMBOLS = [
     "gs_verify_batch_rlc_dev", "gs_verify_batch_rlc", "gs_gt_finalize",
     "gs_verify_batch_rlc_locate_dev", "gs_verify_batch_rlc_locate",
     "gs_verify_statements_rlc_dev", "gs_verify_statements_rlc",
+    "gs_verify_equation_rlc_dev", "gs_verify_equation_rlc",
     "gs_prove_statement_dev", "gs_prove_statement", "gs_verify_statement_dev", "gs_verify_statement",
     "gs_mat_left_mul_com1", "gs_mat_left_mul_com2", "gs_pairing_sum", "gs_fr_matmul",
     "gs_g1_mul_batch", "gs_g2_mul_batch", "gs_g1_mul_batch_dev", "gs_g2_mul_batch_dev",
@@ -233,7 +234,8 @@ class Engine:
 
     def set_option(self, key, value):
         """Planner override (include/gs_amd.h, gs_set_option): miller_twin, miller_ch, var_tm, var_mo, var_w, red_k, coop_fe, line_tables,
-        overlap; locate_k (0 | 2 | 4 | 8): the arity of verify_batch_rlc_locate's product tree.  Results never change,
+        overlap; locate_k (0 | 2 | 4 | 8): the arity of verify_batch_rlc_locate's product tree; eq_pi (-1 | 0 | 1): whether
+        verify_equation_rlc pairs pi per proof or folds it across the batch in G2.  Results never change,
         only which kernel shapes run (locate_k changes which nodes exist, hence info[1] and what can cancel)."""
         self._chk(self.lib.gs_set_option(self.ctx, key.encode(), int(value)))
 
@@ -453,7 +455,8 @@ class Engine:
         """The batched (RLC) verifiers, host and _dev forms: byte lengths, missing outputs, the call.  arrays: A ..
         theta as verify_batch takes them; S: statements of N = E equations each over shared commitments (None: one
         unshared batch of N); outs: the entry's outputs in the order of its C signature.  A host form's missing output
-        is allocated here, a _dev form's is refused.  Returns outs."""
+        is allocated here, a _dev form's is refused.  Returns outs.  gs_verify_equation_rlc[_dev]: N proofs of ONE
+        equation -- A, B, Gamma, target are sized as one copy (csrc/gs_layout.h, Layout::one_equation)."""
         dev, stmt = fn.endswith("_dev"), S is not None
         if not dev:
             rho = np.ascontiguousarray(rho, dtype=np.uint64).reshape(-1)
@@ -464,6 +467,8 @@ class Engine:
             raise GsError(1, "%s: bad equation type or empty variable list" % fn)
         k = S if stmt else 1  # combined checks: copies of the layout, accumulator pairs
         one = self._sizes(ty, N, m, n, stmt)
+        if fn.startswith("gs_verify_equation_rlc"):
+            one.update({key: self._sizes(ty, 1, m, n)[key] for key in ("A", "B", "Gamma", "target")})
         want = dict(rho=32 * k * N, acc=k * 2 * self.GT, ok=S if stmt else N, ok_all=1, info=8)
         keys = ("A", "B", "Gamma", "target", "xcoms", "ycoms", "pi", "theta")
         _need(fn, [(key, a, k * one[key]) for key, a in zip(keys, arrays)] +
@@ -499,6 +504,14 @@ class Engine:
         o = self._rlc("gs_verify_statements_rlc", ty, S, E, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
                       acc=None, ok=None)
         return o["ok"], o["acc"].reshape(S, 2, self.GT)
+
+    def verify_equation_rlc(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho):
+        """Batched verifier for N proofs of ONE equation (host buffers): A[n], B[m], Gamma[m][n], target[1] in one copy,
+        xcoms[N][m], ycoms[N][n], pi[N][kx], theta[N][ky] per proof.  rho: uint64[N*4], non-zero, from a CSPRNG (the
+        rho contract of gs_amd.h).  Returns (ok_all, acc_pair_bytes) in the convention of verify_batch_rlc."""
+        o = self._rlc("gs_verify_equation_rlc", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
+                      acc=None, ok_all=None)
+        return int(o["ok_all"][0]), o["acc"]
 
     def gt_finalize_dev(self, accs_dev, count):
         """the same with `count` pairs in device memory (torch tensor)."""
@@ -600,6 +613,11 @@ class Engine:
         (asynchronous)."""
         self._rlc("gs_verify_batch_rlc_locate_dev", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta),
                   rho, acc=acc, ok=ok, info=info)
+
+    def verify_equation_rlc_dev(self, ty, N, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc):
+        """Device form: the constants in one copy, rho uint64[N*4], acc one accumulator pair (asynchronous)."""
+        self._rlc("gs_verify_equation_rlc_dev", ty, None, N, m, n, (A, B, Gamma, target, xcoms, ycoms, pi, theta), rho,
+                  acc=acc)
 
     def verify_statements_rlc_dev(self, ty, S, E, m, n, A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok):
         """Device form: rho uint64[S*E*4], acc S accumulator pairs, ok S bytes, all on the device (asynchronous)."""

@@ -111,6 +111,7 @@ struct gs_ctx {
   int var_mo = 0, var_w = 0;  // outputs per Straus lane (1, 2, 4) and its window width (4, 5); 0 = planned
   int miller_ch = 0, miller_twin = -1;
   int coop_fe = 1;  // 0 never, 1 when one lane per final exponentiation cannot fill the chip, 2 always
+  int eq_pi = -1;    // gs_verify_equation_rlc's pi term: 0 per-proof pairs, 1 folded in G2 across the batch; -1 = planned
   int locate_k = 0;  // arity of gs_verify_batch_rlc_locate's product tree (2, 4, 8); 0 = planned (8, as gt_product)
   bool line_tables = true;  // pairs whose G2 argument is a CRS element read precomputed Miller lines
   // host-pointer entry points (HostPipe below): pinned staging, a copy stream, memcpy workers, per-array events
@@ -832,8 +833,9 @@ template <class Body, class... A> static int go_seg(gs_ctx* c, const LaunchRec* 
   }
   return GS_OK;
 }
+// The record of a launch: what launch_seg_typed launches or notes, and what seg_pair merges
 template <class Body, class... A, class... U>
-static int launch_seg_typed(gs_ctx* c, const char* name, void (*)(size_t, A...), size_t total, int block, U&&... u) {
+static LaunchRec seg_rec_typed(gs_ctx* c, const char* name, void (*)(size_t, A...), size_t total, int block, U&&... u) {
   static_assert(sizeof...(A) == sizeof...(U), "argument count of the kernel body");
   static_assert(sizeof(Segs<A...>) <= 3800, "the segment table travels as a kernel argument");
   LaunchRec r;
@@ -846,6 +848,11 @@ static int launch_seg_typed(gs_ctx* c, const char* name, void (*)(size_t, A...),
   Pack<A...> pk{{static_cast<A>(u)}...};
   r.pack.assign((const uint8_t*)&pk, (const uint8_t*)&pk + sizeof pk);
   r.go = &go_seg<Body, A...>;
+  return r;
+}
+template <class Body, class... A, class... U>
+static int launch_seg_typed(gs_ctx* c, const char* name, void (*sig)(size_t, A...), size_t total, int block, U&&... u) {
+  LaunchRec r = seg_rec_typed<Body>(c, name, sig, total, block, std::forward<U>(u)...);
   if (c->rec) {
     if (total) c->rec->parts[c->rec->cur].push_back(std::move(r));
     return GS_OK;
@@ -853,6 +860,22 @@ static int launch_seg_typed(gs_ctx* c, const char* name, void (*)(size_t, A...),
   if (total == 0) return GS_OK;
   const LaunchRec* rp = &r;
   return r.go(c, &rp, 1);
+}
+template <class Body, class... U> static LaunchRec seg_rec(gs_ctx* c, const char* name, size_t total, int block, U&&... u) {
+  typedef decltype(&Body::run) Sig;
+  return seg_rec_typed<Body>(c, name, (Sig) nullptr, total, block, std::forward<U>(u)...);
+}
+// Two independent launches of ONE body as the two segments of one launch (a's lanes first); under the kernel
+// profile they go out one after the other so that each keeps its own name, time and work.
+static int seg_pair(gs_ctx* c, const LaunchRec& a, const LaunchRec& b) {
+  if (c->rec) return fail(c, GS_ERR_ARG, "internal: this kernel cannot be part of a merged launch");
+  const LaunchRec* both[2] = {&a, &b};
+  if (c->prof || a.total == 0 || b.total == 0) {
+    for (const LaunchRec* r : both)
+      if (r->total) RC(r->go(c, &r, 1));
+    return GS_OK;
+  }
+  return a.go(c, both, 2);
 }
 template <class Body, class... U> static int launch_seg(gs_ctx* c, const char* name, size_t total, int block, U&&... u) {
   typedef decltype(&Body::run) Sig;  // void (*)(size_t g, args...): the body's own parameter types
@@ -2276,6 +2299,232 @@ template <class C> struct Impl {
     return GS_OK;
   }
 
+  // Sum, across the `rows` rows of a device array, of the first `count` Com-shaped elements of every row (group F):
+  // K-ary levels of k_batch_sum (K = 8) down to one row of Jacobian partials, then k_red: `count` normalised elements
+  // at `out`, one shared inversion per lane.
+  template <class F>
+  static int batch_sum(gs_ctx* c, const std::string& tag, size_t rows, int count, const void* in, uint32_t row_bytes,
+                       void* out) {
+    const int K = 8, cols = 2 * count;
+    const size_t com = 2 * AFFB(C, F);
+    void *b0, *b1;
+    const size_t r1 = (rows + K - 1) / K;
+    RC(scratch(c, (tag + ".l0").c_str(), r1 * cols * sizeof(Jac<F>), &b0));
+    RC(scratch(c, (tag + ".l1").c_str(), ((r1 + K - 1) / K) * cols * sizeof(Jac<F>), &b1));
+    const std::string kn = "k_batch_sum" + tag;
+    const Jac<F>* cur = nullptr;
+    Jac<F>*dst = (Jac<F>*)b0, *other = (Jac<F>*)b1;
+    for (size_t len = rows;;) {  // (a single row still goes through level 0: affine in, Jacobian out)
+      const size_t lo = (len + K - 1) / K, total = lo * cols;
+      c->work_hint = len * (uint64_t)cols;  // points summed
+      RC((launch_seg<k_batch_sum<C, F>>(c, kn.c_str(), total, 64, total, len, cols, cur ? nullptr : (const uint8_t*)in,
+                                        row_bytes, cur, dst, K)));
+      cur = dst;
+      std::swap(dst, other);
+      len = lo;
+      if (len == 1) break;
+    }
+    RedLaunch r;
+    r.name = "k_red" + tag;
+    r.tag = tag;
+    for (int q = 0; q < count; q++) r.hred.push_back(mkred(2 * q, 2 * q + 1, 2 * q + 1, 2 * q + 2, 0, q));
+    r.part = cur;
+    r.nred = r.hred.size();
+    r.nslots = cols;
+    r.outs = out_tab(out, (uint32_t)(count * com));
+    return run_red<C, F>(c, 1, r);
+  }
+
+  // N proofs of ONE equation: the constants A, B, Gamma, target exist once, so the random linear
+  // combination is taken ACROSS the proofs before pairing wherever the other argument of a pair is a constant or a CRS
+  // element.  In the notation of rlc_front (C'_e,ib, Th'_e,lb per proof e; r_ab = sum_e rho_e,ab):
+  //   per proof   e(P'_e,jb, d_e,j.b),  P'_e,jb = rho_e,1b A_j + sum_i Gamma_ij C'_e,ib       2n pairs
+  //               [eq_pi = 0: e(-U'_e,kb, pi_e,k.b), U'_e,kb = rho_e,0b u_k.0 + rho_e,1b u_k.1   2kx pairs]
+  //   per batch   e(sum_e C'_e,i1, B_i)  |  e(PB_b, W2.b),  PB_b = sum_i b_i sum_e C'_e,ib [- r_1b t] [- sum_a r_ab t W1.a]
+  //               [eq_pi = 1: e(-u_k.a, sum_e sum_b rho_e,ab pi_e,k.b)]
+  //               e(-sum_e Th'_e,lb, v_l.b)      [MSMEG2: e(-(r_01 W1.0 + r_11 W1.1), t)]      target: t^(r_11)
+  // Scalars: a pool per proof (rho, a_j rho) and ONE shared pool (Gamma, b, r, -t r), which the per-proof pass over
+  // Gamma reads with a pool stride of 0.  So that this pass needs shared scalars only, rho_e,1b A_j (a_j rho_e,ab W1.a)
+  // is an output of pass 1 and enters P' as the affine addend of a fixed-base lane without fixed-base terms.
+  static int verify_eq_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                           const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                           const uint64_t* rho, void* acc) {
+    const bool xg = x_is_group(ty), yg = y_is_group(ty);
+    const int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
+    // planned: pi per proof, as measured at 2^14 for PPE and QuadEqu; folded in G2 where a proof has two pi elements and
+    // the batch has 2^16 proofs or more (the fold is ahead there for PPE; profiles/eq_rlc/rate.json)
+    const bool fold_pi = c->eq_pi >= 0 ? c->eq_pi == 1 : (kx == 2 && N >= ((size_t)1 << 16));
+    RangeGuard rg_all("gs.verify_eq_rlc");
+    PoolMap pp, ps;  // per proof, shared
+    memset(&pp, 0, sizeof pp);
+    memset(&ps, 0, sizeof ps);
+    pp.RH = 0;
+    pp.AR = 4;
+    pp.total = 4 + (xg ? 0 : 4 * n);
+    ps.GC = 0;
+    ps.BC = m * n;
+    ps.RH = ps.BC + m;
+    ps.NR = ps.RH + 4;
+    ps.total = ps.NR + 4;
+    void *pool, *spool, *sums;
+    RC(scratch(c, "eqrlc.pool", N * pp.total * sizeof(S), &pool));
+    RC(scratch(c, "eqrlc.spool", ps.total * sizeof(S), &spool));
+    RC(scratch(c, "eqrlc.sums", 8 * sizeof(unsigned long long), &sums));
+    HIPCHK(c, hipMemsetAsync(sums, 0, 8 * sizeof(unsigned long long), c->cur ? c->cur : c->stream));
+    RC(launch(c, "k_prep_verify_eq_rlc", k_prep_verify_eq_rlc<C>, (N + 63) / 64 * 64, 64, N, n, xg ? nullptr : (const S*)A,
+              rho, pp, (S*)pool, (unsigned long long*)sums));
+    {
+      const size_t lanes = std::max((size_t)m * n, (size_t)1);
+      RC(launch(c, "k_prep_verify_eq_rlc.shared", k_prep_verify_eq_rlc_shared<C>, lanes, 64, m, n, (const S*)G,
+                yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, (const unsigned long long*)sums,
+                ps, (S*)spool));
+    }
+    auto RH = [&](int a, int b) { return 2 * a + b; };  // + pp.RH (per proof) or ps.RH (the sums)
+    // terms per Straus lane: "var_tm" forces it; endo = 0: one plain double-and-add lane per term, as everywhere else
+    auto TM = [&](int planned) { return !c->endo ? 1 : c->var_tm > 0 ? c->var_tm : planned; };
+    // ---- pass 1 (per proof): C'_i (m), Th'_l (ky), RA_j = rho_1b A_j | sum_a a_j rho_ab W1.a (n), [U'_k (kx)]
+    const int iTh = m, iRA = m + ky, iU = iRA + n, n1 = iU + (fold_pi ? 0 : kx);
+    void* s1;
+    RC(scratch(c, "eqrlc.s1", N * n1 * Z::COM1, &s1));
+    {
+      SidePlan sp;
+      sp.tm = TM(4);
+      ComOutputs{sp}.add(n1, 0, 0, [&](int q, int b, ComOutputs& o) {
+        if (q < iRA) {
+          const int arr = q < m ? 0 : 1, idx = q < m ? q : q - m;
+          o.terms({mkvar(pp.RH + RH(0, b), arr, 2 * idx, 0), mkvar(pp.RH + RH(1, b), arr, 2 * idx + 1, 0)});
+        } else if (q < iU) {
+          const int j = q - iRA;
+          if (xg)
+            o.terms({mkvar(pp.RH + RH(1, b), 2, j, 0)});
+          else
+            o.fix(pp.AR + j * 4 + 0 + b, tb_w(0), pp.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0);
+        } else {
+          const int k = q - iU;
+          o.fix(pp.RH + RH(0, b), tb_u(k, 0), pp.RH + RH(1, b), tb_u(k, 1), 0xFF, 0);
+        }
+      });
+      const ArrTab arrs = arr_tab({{0, xcoms, (uint32_t)(m * Z::COM1)}, {1, theta, (uint32_t)(ky * Z::COM1)}, {2, A, 0, xg}});
+      const OutTab outs = out_tab(s1, (uint32_t)(n1 * Z::COM1));
+      RC((run_side<C, F1>(c, ".q1", N, sp, arrs, (const S*)pool, pp.total, (const A1*)c->tabs->tab16_g1.p, outs)));
+    }
+    // ---- pass 2 (per proof, shared scalars): P'_j = RA_j + sum_i Gamma_ij C'_i
+    void* s2;
+    RC(scratch(c, "eqrlc.s2", N * n * Z::COM1, &s2));
+    {
+      SidePlan sp;
+      sp.tm = TM(8);
+      ComOutputs{sp}.add(n, 0, 0, [&](int j, int b, ComOutputs& o) {
+        std::vector<VarTask> terms;
+        for (int i = 0; i < m; i++) terms.push_back(mkvar(ps.GC + i * n + j, 0, 2 * i + b, 0));
+        o.fix(0, 0xFF, 0, 0xFF, 0, 2 * (iRA + j) + b);
+        o.terms(terms);
+      });
+      const ArrTab arrs = arr_tab({{0, s1, (uint32_t)(n1 * Z::COM1)}});
+      const OutTab outs = out_tab(s2, (uint32_t)(n * Z::COM1));
+      RC((run_side<C, F1>(c, ".q2", N, sp, arrs, (const S*)spool, 0, (const A1*)c->tabs->tab16_g1.p, outs)));
+    }
+    // ---- across the batch: sum_e C'_e,i and sum_e Th'_e,l (the first m + ky elements of every row of s1)
+    void* ssum;
+    RC(scratch(c, "eqrlc.ssum", (m + ky) * Z::COM1, &ssum));
+    RC(batch_sum<F1>(c, ".eqs1", N, m + ky, s1, (uint32_t)(n1 * Z::COM1), ssum));
+    // ---- folded pi: Pi_e,k.a = sum_b rho_e,ab pi_e,k.b per proof (short terms), then their sum in G2
+    void* pisum = nullptr;
+    if (fold_pi) {
+      void* s3;
+      RC(scratch(c, "eqrlc.s3", N * kx * Z::COM2, &s3));
+      SidePlan sp;
+      sp.tm = TM(8);
+      ComOutputs{sp}.add(kx, 0, 0, [&](int k, int a, ComOutputs& o) {
+        o.terms({mkvar(pp.RH + RH(a, 0), 0, 2 * k + 0, 0), mkvar(pp.RH + RH(a, 1), 0, 2 * k + 1, 0)});
+      });
+      const ArrTab arrs = arr_tab({{0, pi, (uint32_t)(kx * Z::COM2)}});
+      const OutTab outs = out_tab(s3, (uint32_t)(kx * Z::COM2));
+      RC((run_side<C, F2>(c, ".q3", N, sp, arrs, (const S*)pool, pp.total, (const A2*)c->tabs->tab16_g2.p, outs)));
+      RC(scratch(c, "eqrlc.pisum", kx * Z::COM2, &pisum));
+      RC(batch_sum<F2>(c, ".eqs2", N, kx, s3, (uint32_t)(kx * Z::COM2), pisum));
+    }
+    // ---- batch-level G1 outputs (one "equation", shared pool): [PB] (scalar b), [W1'] (MSMEG2)
+    const int iPB = 0, iW = yg ? 0 : 1, nb = iW + (ty == GS_MSMEG2 ? 1 : 0);
+    void* sb = nullptr;
+    if (nb) {
+      RC(scratch(c, "eqrlc.sb", nb * Z::COM1, &sb));
+      SidePlan sp;
+      sp.tm = yg ? 1 : TM(8);  // (MSMEG2's only output has no variable-base term)
+      ComOutputs{sp}.add(nb, 0, 0, [&](int q, int b, ComOutputs& o) {
+        std::vector<VarTask> terms;
+        if (!yg && q == iPB) {
+          for (int i = 0; i < m; i++) terms.push_back(mkvar(ps.BC + i, 0, 2 * i + b, 0));  // b_i sum_e C'_e,ib
+          if (ty == GS_MSMEG1) {
+            VarTask v = mkvar(ps.RH + RH(1, b), 1, 0, 0);  // - r_1b t
+            v.neg = 1;
+            terms.push_back(v);
+          }
+          if (ty == GS_QUAD) o.fix(ps.NR + 0 + b, tb_w(0), ps.NR + 2 + b, tb_w(1), 0xFF, 0);
+        } else {
+          o.fix(ps.RH + RH(0, b), tb_w(0), ps.RH + RH(1, b), tb_w(1), 0xFF, 0);
+        }
+        o.terms(terms);
+      });
+      const ArrTab arrs = arr_tab({{0, ssum, 0}, {1, target, 0, ty == GS_MSMEG1}});
+      const OutTab outs = out_tab(sb, (uint32_t)(nb * Z::COM1));
+      RC((run_side<C, F1>(c, ".q4", 1, sp, arrs, (const S*)spool, 0, (const A1*)c->tabs->tab16_g1.p, outs)));
+    }
+    // ---- Miller.  Per proof: P arrays 0 = s2, 1 = s1; Q arrays 0 ycoms, 3 pi
+    std::vector<PairRef> pr, prb;
+    for (int b = 0; b < 2; b++) {
+      for (int j = 0; j < n; j++) add_pair(pr, 0, 2 * j + b, 0, 0, 2 * j + b);
+      if (!fold_pi)
+        for (int k = 0; k < kx; k++) add_pair(pr, 1, 2 * (iU + k) + b, 1, 3, 2 * k + b);
+    }
+    // per batch: P arrays 0 = sb, 1 = ssum, 2 = crs G1 (u, W1); Q arrays 1 B, 2 crs G2 (v, W2), 3 = pisum, 4 target
+    for (int b = 0; b < 2; b++) {
+      if (yg) {
+        if (b == 1)
+          for (int i = 0; i < m; i++) add_pair(prb, 1, 2 * i + 1, 0, 1, i);
+      } else {
+        add_pair(prb, 0, 2 * iPB + b, 0, 2, 4 + b);
+      }
+      for (int l = 0; l < ky; l++) add_pair(prb, 1, 2 * (iTh + l) + b, 1, 2, 2 * l + b);
+      if (fold_pi)
+        for (int k = 0; k < kx; k++) add_pair(prb, 2, 2 * k + b, 1, 3, 2 * k + b);  // (-u_k.a, Pi_k.a), a = b here
+      if (ty == GS_MSMEG2 && b == 1) add_pair(prb, 0, 2 * iW + 1, 1, 4, 0);
+    }
+    const std::vector<MillerTask> mt = plan_miller_single(c, N, pr), mtb = plan_miller_single(c, 1, prb);
+    const int ntask = (int)mt.size(), ntb = (int)mtb.size();
+    const size_t nparts = N * ntask + ntb;
+    void *mpart, *tmp, *pt;
+    RC(scratch(c, "eqrlc.mpart", nparts * sizeof(GT), &mpart));
+    RC(scratch(c, "eqrlc.tmp", (nparts / 4 + 8) * sizeof(GT), &tmp));
+    RC(scratch(c, "eqrlc.t", sizeof(GT), &pt));
+    {
+      const MillerTask *dmt, *dmtb;
+      RC(upload(c, "eqrlc.mt", mt, &dmt));
+      RC(upload(c, "eqrlc.mtb", mtb, &dmtb));
+      const ArrTab parr = arr_tab({{0, s2, (uint32_t)(n * Z::COM1)}, {1, s1, (uint32_t)(n1 * Z::COM1)}});
+      const ArrTab qarr = arr_tab({{0, ycoms, (uint32_t)(n * Z::COM2)}, {3, pi, (uint32_t)(kx * Z::COM2)}});
+      // the batch-level pairs are one wave: they ride along as a second segment of the per-proof launch (a launch of
+      // their own would add a serial Miller lane to every call: k_miller.eqrlc.batch in profiles/eq_rlc/rate.json)
+      miller_work_hint(c, N, mt, false);
+      const LaunchRec per = seg_rec<k_miller<C, false>>(c, "k_miller.eqrlc", N * ntask, 64, N * ntask, ntask, dmt, parr,
+                                                        qarr, (GT*)mpart, 1, lines(c));
+      const ArrTab parb = arr_tab({{0, sb, 0, nb > 0}, {1, ssum, 0}, {2, c->tabs->crs_g1.p, 0}});
+      const ArrTab qarb = arr_tab({{1, B, 0, yg}, {2, c->tabs->crs_g2.p, 0}, {3, pisum, 0, fold_pi}, {4, target, 0, ty == GS_MSMEG2}});
+      miller_work_hint(c, 1, mtb, false);
+      const LaunchRec bat = seg_rec<k_miller<C, false>>(c, "k_miller.eqrlc.batch", (size_t)ntb, 64, (size_t)ntb, ntb, dmtb,
+                                                        parb, qarb, (GT*)mpart + N * ntask, 1, lines(c));
+      RC(seg_pair(c, bat, per));  // (the single wave in the first block of the grid)
+    }
+    uint8_t* a = (uint8_t*)acc;
+    RC(gt_product(c, nparts, (GT*)mpart, (GT*)tmp, a));
+    if (ty == GS_PPE)
+      RC(launch(c, "k_eq_rlc_tpow", k_eq_rlc_tpow<C>, 1, 64, (const uint8_t*)target, (const S*)spool + ps.RH + 3, (GT*)pt));
+    else
+      RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, (GT*)pt));
+    RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)pt, a + Z::GT));
+    return GS_OK;
+  }
+
   // The batched verifier with fault localisation.  Same front; the products are a K-ary tree whose
   // levels are KEPT: level 0 = the N leaves (f_e, t_e), level l = products of runs of K of level l - 1, one node at the
   // top.  The descent then runs from the root down, one launch per level, each sized for the whole level: the frontier
@@ -2966,6 +3215,9 @@ int gs_set_option(gs_ctx* c, const char* key, int value) {
   } else if (k == "locate_k") {
     if (value != 0 && value != 2 && value != 4 && value != 8) return fail(c, GS_ERR_ARG, "locate_k: 0 (planned), 2, 4, 8");
     c->locate_k = value;
+  } else if (k == "eq_pi") {
+    if (value < -1 || value > 1) return fail(c, GS_ERR_ARG, "eq_pi: -1 (planned), 0 per-proof pairs, 1 folded in G2");
+    c->eq_pi = value;
   } else if (k == "dlog_steps") {
     if (value < 0) return fail(c, GS_ERR_ARG, "dlog_steps: 0 (default) or the giant steps per launch");
     c->dlog_steps = value;
@@ -3887,15 +4139,17 @@ int gs_fr_matmul(gs_ctx* c, int rows, int inner, int cols, const void* lhs, cons
                        fr_matmul_impl<Bn254>(c, rows, inner, cols, lhs, rhs, out));
 }
 
-// ---- batched (RLC) verifiers: one combined check per batch, the same with fault localisation, one per Statement -----
-// All three move the verifier's eight inputs, the exponents rho and up to three outputs.  rlc_arrays states a call's
-// arrays ONCE; the checks of the six entry points and the staging of the three host forms walk that list.
-enum RlcVariant { RLC_PLAIN, RLC_LOCATE, RLC_STMT };
+// ---- batched (RLC) verifiers: one combined check per batch, the same with fault localisation, one per Statement, one
+// per batch of proofs of ONE equation -----
+// All four move the verifier's eight inputs, the exponents rho and up to three outputs.  rlc_arrays states a call's
+// arrays ONCE; the checks of the eight entry points and the staging of the four host forms walk that list.
+enum RlcVariant { RLC_PLAIN, RLC_LOCATE, RLC_STMT, RLC_EQ };
 enum { RLC_RHO = 8, RLC_ACC, RLC_OK, RLC_INFO, RLC_MAX };
 struct RlcCall {
   RlcVariant v;
   int ty;
   size_t S, N;  // RLC_STMT: S statements of N = E equations each over shared commitments; otherwise S = 1
+                // (RLC_EQ: N proofs of one equation -- A, B, Gamma, target are ONE copy)
   int m, n;
   // A, B, Gamma, target, xcoms, ycoms, pi, theta, rho, acc, ok (not RLC_PLAIN), info (RLC_LOCATE): host pointers at the
   // un-suffixed entry points, device pointers at the _dev ones and inside
@@ -3912,24 +4166,29 @@ struct RlcArr {
 static int rlc_arrays(const gs_ctx* c, const RlcCall& k, RlcArr* a) {
   static const lay::Array in[8] = {lay::A, lay::B, lay::GAMMA, lay::TARGET, lay::XCOMS, lay::YCOMS, lay::PI, lay::THETA};
   const size_t fq = sz_fq(c->curve);
-  const lay::Layout L(fq, k.ty, k.N, k.m, k.n, k.v == RLC_STMT);  // one statement = the shared layout with N = E
+  // one statement = the shared layout with N = E; RLC_EQ: the layout whose constants are one copy
+  const lay::Layout L = k.v == RLC_EQ ? lay::Layout::one_equation(fq, k.ty, k.N, k.m, k.n)
+                                      : lay::Layout(fq, k.ty, k.N, k.m, k.n, k.v == RLC_STMT);
   int na = 0;
   for (; na < 8; na++) a[na] = {lay::kArrayName[in[na]], k.p[na], k.S * L.bytes[in[na]], ARR_IN};
   a[na++] = {"rho", k.p[RLC_RHO], 4 * k.S * k.N * sizeof(uint64_t), ARR_IN};        // four exponents per equation
   a[na++] = {"acc", k.p[RLC_ACC], k.S * 2 * 12 * fq, ARR_OUT | ARR_OPT};            // one GT pair per combined check
-  if (k.v != RLC_PLAIN) a[na++] = {"ok", k.p[RLC_OK], k.v == RLC_STMT ? k.S : k.N, ARR_OUT};
+  if (k.v == RLC_LOCATE || k.v == RLC_STMT) a[na++] = {"ok", k.p[RLC_OK], k.v == RLC_STMT ? k.S : k.N, ARR_OUT};
   if (k.v == RLC_LOCATE) a[na++] = {"info", k.p[RLC_INFO], 2 * sizeof(uint32_t), ARR_OUT | ARR_OPT};
   return na;
 }
-// everything the six entry points refuse; fills a[] / *na for the caller
+// everything the eight entry points refuse; fills a[] / *na for the caller
 static int rlc_check(gs_ctx* c, const RlcCall& k, bool host, RlcArr* a, int* na) {
   RC(check_ctx(c, true));
+  if (k.v == RLC_EQ && c->rec) return fail(c, GS_ERR_ARG, "gs_verify_equation_rlc inside a mixed call");
   RC(check_shape(c, k.ty, k.m, k.n));
   if (k.S == 0 || k.N == 0)
     return fail(c, GS_ERR_ARG, k.v == RLC_STMT ? "empty batch: S and E must be >= 1" : "empty batch");
   // what the plan cannot index is refused
   if (k.v == RLC_LOCATE && k.N >= ((size_t)1 << 32) / 8)
     return fail(c, GS_ERR_SHAPE, "gs_verify_batch_rlc_locate: node indices are 32-bit");
+  if (k.v == RLC_EQ && k.N >= ((size_t)1 << 32))  // the halves of rho are summed in 64 bits (k_prep_verify_eq_rlc)
+    return fail(c, GS_ERR_SHAPE, "gs_verify_equation_rlc: at most 2^32 - 1 proofs per call");
   if (k.v == RLC_STMT) {  // arrays strided per STATEMENT in 32-bit bytes, 32-bit task tables and pool offsets
     const size_t E = k.N, lim = (size_t)1 << 32;
     const int m = k.m, n = k.n;
@@ -3972,11 +4231,14 @@ static int rlc_run(gs_ctx* c, const RlcCall& k) {
     case RLC_STMT:
       return DISPATCH(c, verify_stmt_rlc(c, k.ty, k.S, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7],
                                          rho, k.out(RLC_ACC), ok));
+    case RLC_EQ:
+      return DISPATCH(c, verify_eq_rlc(c, k.ty, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], rho,
+                                       k.out(RLC_ACC)));
   }
   return GS_ERR_ARG;
 }
-// Any of the six: device pointers run as they are; host pointers are staged in, run and the outputs copied back.
-// ok_all (gs_verify_batch_rlc only; may be NULL): gs_gt_finalize on the returned pair.
+// Any of the eight: device pointers run as they are; host pointers are staged in, run and the outputs copied back.
+// ok_all (gs_verify_batch_rlc and gs_verify_equation_rlc only; may be NULL): gs_gt_finalize on the returned pair.
 static int rlc_call(gs_ctx* c, const RlcCall& k, bool host, uint8_t* ok_all = nullptr) {
   RlcArr a[RLC_MAX];
   int na;
@@ -4032,6 +4294,17 @@ int gs_verify_statements_rlc(gs_ctx* c, int ty, size_t S, size_t E, int m, int n
                              const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
                              const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
   return rlc_call(c, {RLC_STMT, ty, S, E, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc, ok}}, true);
+}
+// N proofs of ONE equation: the constants are one copy, the combination is taken across the proofs before pairing
+int gs_verify_equation_rlc_dev(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                               const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                               const void* theta, const uint64_t* rho, void* acc) {
+  return rlc_call(c, {RLC_EQ, ty, 1, N, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc}}, false);
+}
+int gs_verify_equation_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                           const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                           const uint64_t* rho, void* acc, uint8_t* ok_all) {
+  return rlc_call(c, {RLC_EQ, ty, 1, N, m, n, {A, B, G, target, xcoms, ycoms, pi, theta, rho, acc}}, true, ok_all);
 }
 int gs_gt_finalize_dev(gs_ctx* c, size_t count, const void* accs_dev, uint8_t* ok) {
   RC(check_ctx(c, false));

@@ -822,6 +822,114 @@ __global__ void __launch_bounds__(64, GS_WPE) k_rlc_tpow(size_t N, const uint8_t
   out_t[e] = h;
 }
 
+// ---- one equation, N proofs (gs_verify_equation_rlc) -------------------------------------------------
+// Fr preparation.  The constants exist ONCE, so the scalars live in two pools:
+//   per proof (pm.total scalars each):  RH[2a + b] = rho[e][2a + b];  AR[4j + 2a + b] = a_j rho_e,ab (scalar a only)
+//   shared (one copy, k_prep_verify_eq_rlc_shared): Gamma, b, the sums r_ab and -t r_ab
+// The sums r_ab = sum_e rho_e,ab are taken here as well, because a _dev caller's rho is device memory: every wave adds
+// the low and the high 32-bit halves of its 64 exponents separately into sums[2c], sums[2c + 1] (u64 each: exact below
+// 2^32 proofs, whatever order the atomics land in), and the shared kernel puts the halves together.
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE)
+    k_prep_verify_eq_rlc(size_t N, int n, const Fr<C>* as, const uint64_t* rho, PoolMap pm, Fr<C>* pool,
+                         unsigned long long* sums) {
+  size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = e < N;
+  unsigned long long part[8];
+  Fr<C> rm[4];
+  for (int c = 0; c < 4; c++) {
+    uint64_t v = live ? rho[e * 4 + c] : 0;
+    part[2 * c] = v & 0xFFFFFFFFull;
+    part[2 * c + 1] = v >> 32;
+    Fr<C> r = fzero<FrM<C>>();
+    r.v[0] = (uint32_t)v;
+    r.v[1] = (uint32_t)(v >> 32);
+    if (live) pool[e * pm.total + pm.RH + c] = r;  // canonical (rho < 2^64 < r)
+    rm[c] = to_mont(r);
+  }
+  if (live && as)
+    for (int j = 0; j < n; j++)
+      for (int c = 0; c < 4; c++) pool[e * pm.total + pm.AR + j * 4 + c] = from_mont(mul(as[j], rm[c]));
+  for (int k = 0; k < 8; k++) {  // (every lane of the wave takes part: lanes past N hold zeros)
+    unsigned long long v = part[k];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    if (threadIdx.x == 0 && v) atomicAdd(sums + k, v);
+  }
+}
+// the shared pool: lane g converts Gamma[g] and b[g]; lane 0 also assembles r_c = sums[2c] + 2^32 sums[2c + 1] (below
+// 2^96) as a canonical Fr (RH) and, for QuadEqu, NR[c] = -t r_c
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE)
+    k_prep_verify_eq_rlc_shared(int m, int n, const Fr<C>* G, const Fr<C>* bs, const Fr<C>* tq,
+                                const unsigned long long* sums, PoolMap pm, Fr<C>* pool) {
+  size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < (size_t)m * n) pool[pm.GC + g] = from_mont(G[g]);
+  if (bs && g < (size_t)m) pool[pm.BC + g] = from_mont(bs[g]);
+  if (g != 0) return;
+  for (int c = 0; c < 4; c++) {
+    const unsigned long long lo = sums[2 * c], hi = sums[2 * c + 1];
+    const unsigned long long w0 = lo + (hi << 32), w1 = (hi >> 32) + (w0 < lo ? 1ull : 0ull);
+    Fr<C> r = fzero<FrM<C>>();
+    r.v[0] = (uint32_t)w0;
+    r.v[1] = (uint32_t)(w0 >> 32);
+    r.v[2] = (uint32_t)w1;
+    r.v[3] = (uint32_t)(w1 >> 32);
+    pool[pm.RH + c] = r;
+    if (tq) pool[pm.NR + c] = from_mont(mul(neg(tq[0]), to_mont(r)));
+  }
+}
+// t^(r_11): ONE power for the whole batch (PPE; boundary in, internal out).  The exponent is the canonical r_11 of the
+// shared pool (below 2^96); general squarings, as k_rlc_tpow: the target is raised without a subgroup check.
+template <class C>
+__global__ void __launch_bounds__(64, GS_WPE) k_eq_rlc_tpow(const uint8_t* target, const Fr<C>* r11, Fp12<C>* out_t) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  Fp12<C> t, acc;
+  f12_from_boundary<C>(t, reinterpret_cast<const BFq<C>*>(target));
+  const Fr<C> k = r11[0];
+  f12_one(acc);
+  bool started = false;
+  for (int i = 127; i >= 0; i--) {
+    if (started) f12_sqr(acc, acc);
+    if ((k.v[i >> 5] >> (i & 31)) & 1) {
+      if (started)
+        f12_mul(acc, acc, t);
+      else
+        acc = t;
+      started = true;
+    }
+  }
+  out_t[0] = acc;
+}
+// Segmented K-ary sum ACROSS the batch.  The input is `n_in` rows of `cols` points (column q of every row is summed
+// with column q of the others); lane (r, q) sums rows [K r, K r + K) of column q into a Jacobian partial, and the host
+// repeats the launch on its own output until one row is left, which k_red normalises with one shared inversion.  Level
+// 0 reads affine boundary points (`aff`, `row_bytes` apart; mixed additions), the levels above read the partials.
+// jac_madd / jac_add are the complete forms: identities, equal operands (a doubling) and opposite ones (the identity,
+// Z = 0 exactly) come out right at every level.
+template <class C, class F>
+struct k_batch_sum {
+  static __device__ __forceinline__ void run(size_t g, size_t total, size_t n_in, int cols, const uint8_t* aff,
+                                             uint32_t row_bytes, const Jac<F>* jin, Jac<F>* out, int K) {
+  if (g >= total) return;
+  const size_t r = g / cols, q = g % cols;
+  const size_t lo = r * (size_t)K, hi = lo + K < n_in ? lo + K : n_in;
+  Jac<F> s;
+  if (aff) {
+    Aff<F> a;
+    aff_load<C>(a, aff + lo * (size_t)row_bytes + q * AFFB(C, F));
+    jac_from_aff(s, a);
+    for (size_t i = lo + 1; i < hi; i++) {
+      aff_load<C>(a, aff + i * (size_t)row_bytes + q * AFFB(C, F));
+      jac_madd(s, s, a);
+    }
+  } else {
+    s = jin[lo * cols + q];
+    for (size_t i = lo + 1; i < hi; i++) jac_add(s, s, jin[i * cols + q]);
+  }
+  out[r * cols + q] = s;
+}
+};
+
 // --------------------------------------------------------------------------
 // linear-combination engine
 // --------------------------------------------------------------------------

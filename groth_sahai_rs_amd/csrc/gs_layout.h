@@ -55,6 +55,17 @@ struct Layout {
   }
   // bytes of ONE equation's share of every array: what a block of equations [lo, hi) starts at, times lo
   static Layout stride(size_t fq, int ty, int m, int n) { return Layout(fq, ty, 1, m, n, false); }
+  // N proofs of ONE equation (gs_verify_equation_rlc): commitments and proofs per proof, the constants A, B, Gamma and
+  // the target in one copy
+  static Layout one_equation(size_t fq, int ty, size_t N, int m, int n) {
+    Layout L(fq, ty, N, m, n, false);
+    const Layout one = stride(fq, ty, m, n);
+    L.bytes[A] = one.bytes[A];
+    L.bytes[B] = one.bytes[B];
+    L.bytes[GAMMA] = one.bytes[GAMMA];
+    L.bytes[TARGET] = one.bytes[TARGET];
+    return L;
+  }
 };
 
 }  // namespace gs_layout

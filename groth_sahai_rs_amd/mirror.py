@@ -373,6 +373,35 @@ def verify_batch_locate(equations, com_proofs, crs, rng):
     return [bool(v) for v in ok]
 
 
+def verify_equation_rlc(equation, com_proofs, crs, rng=None, rho=None):
+    """ONE verdict for N CProofs (one EquProof each) of the SAME equation -- N showings of a credential, N ballots --
+    from gs_verify_equation_rlc: the equation's constants cross the ABI once and the random linear combination is
+    taken across the proofs before pairing.  True iff the combined check passes; a batch with a false proof passes with
+    probability 2^-64 over rho, which is drawn here from the caller's CSPRNG `rng` unless `rho` (uint64[N * 4],
+    non-zero; tests only) is given.  Which proofs of a failing batch are bad: verify_batch_locate."""
+    N = len(com_proofs)
+    assert N >= 1
+    ty = equation.TYPE
+    kx, ky = equation._kxky()
+    m, n = len(com_proofs[0].xcoms.coms), len(com_proofs[0].ycoms.coms)
+    assert m >= 1 and n >= 1
+    equation._check_statement_shape(m, n)
+    for cp in com_proofs:
+        assert len(cp.equ_proofs) == 1 and cp.equ_proofs[0].equ_type == ty
+        assert len(cp.xcoms.coms) == m and len(cp.ycoms.coms) == n
+        assert len(cp.equ_proofs[0].pi) == kx and len(cp.equ_proofs[0].theta) == ky
+    if rho is None:
+        rho = _draw_rho(rng, 4 * N)
+    cat = np.concatenate
+    ok, _ = crs.engine.verify_equation_rlc(
+        ty, N, m, n, _cat(equation.a_consts, 0), _cat(equation.b_consts, 0), _flat_mat(equation.gamma),
+        np.asarray(equation.target, dtype=np.uint64).reshape(-1),
+        cat([_cat(cp.xcoms.coms, 0) for cp in com_proofs]), cat([_cat(cp.ycoms.coms, 0) for cp in com_proofs]),
+        cat([_cat(cp.equ_proofs[0].pi, 0) for cp in com_proofs]),
+        cat([_cat(cp.equ_proofs[0].theta, 0) for cp in com_proofs]), rho)
+    return bool(ok)
+
+
 class Statement:
     """`pub type Statement = Vec<dyn Equ>` (statement.rs:109) made usable: a list of equations of ONE type over the same
     variables (statement.rs:24-28: "each equation is defined with respect to the list of variables that span across

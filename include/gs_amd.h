@@ -115,6 +115,9 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  *                   which the confirmation rejects).  Both are test knobs without an environment twin.
  *   "locate_k"      0 planned (8, the arity of the batched verifier's own product) | 2, 4, 8 arity of the product tree of
  *                   gs_verify_batch_rlc_locate[_dev].  A test knob without an environment twin.
+ *   "eq_pi"        -1 planned | 0 gs_verify_equation_rlc[_dev] pairs pi per proof (2kx pairs each, no G2 work) | 1 it folds
+ *                   pi across the batch in G2 (4kx short terms and a sum per proof, 2kx pairs per call).  No environment
+ *                   twin.  The accumulator pair's meaning and the verdict do not depend on it.
  * The same knobs are read ONCE at gs_ctx_create from the environment for experiments without recompiling the caller:
  * GS_MILLER_TWIN, GS_MILLER_CH, GS_VAR_TM, GS_VAR_MO, GS_VAR_W, GS_VAR_W2, GS_RED_K, GS_COOP_FE, GS_LINE_TABLES, GS_OVERLAP,
  * GS_ENDO (same values).
@@ -479,6 +482,44 @@ int gs_verify_statements_rlc_dev(gs_ctx*, int equ_type, size_t S, size_t E, int 
 int gs_verify_statements_rlc(gs_ctx*, int equ_type, size_t S, size_t E, int m, int n, const void* A, const void* B,
                              const void* Gamma, const void* target, const void* xcoms, const void* ycoms, const void* pi,
                              const void* theta, const uint64_t* rho, void* acc_gt, uint8_t* ok);
+/* Batched verifier for N PROOFS OF ONE EQUATION: the public equation (A[n], B[m], Gamma[m][n], target[1]) exists ONCE,
+ * every proof e brings its own xcoms[N][m], ycoms[N][n], pi[N][kx], theta[N][ky]; rho[N][4] u64 as above.  This is the
+ * traffic gs_rerandomize_batch produces (re-shown credentials, ballots, mix-net outputs).  Because the constants are
+ * shared, the random linear combination is taken ACROSS the proofs before pairing wherever the other argument of a pair
+ * is a constant or a CRS element: per proof only the Gamma term is paired, 2n pairs (plus 2kx for pi
+ * unless "eq_pi" = 1); m (or 2) + 2ky (+ 2kx) pairs and ONE target power t^(sum_e rho_e,11) are paid per call.  The
+ * price is a K-ary sum of N points per folded term.
+ * All four equation types, both curves, shapes as everywhere else.  acc_gt[2] (may be NULL for the host entry) receives
+ * the accumulator pair in the convention of gs_verify_batch_rlc, so that pairs of several calls or ranks combine through
+ * gs_gt_finalize: FE(acc[0]) = prod_e prod_cells (lhs / rhs without the PPE target)^rho_e,cell (acc[0] itself is an
+ * un-exponentiated value: only its FE is defined); acc[1] = t^(sum_e rho_e,11) for PPE, one otherwise, a canonical GT
+ * element: byte for byte what gs_verify_batch_rlc writes for the same proofs with the constants replicated N times.
+ * *ok_all (host entry, may be NULL) = 1 iff FE(acc[0]) == acc[1].
+ * RHO CONTRACT (soundness rests on it), that of gs_verify_batch_rlc: every rho is drawn from a CSPRNG, fresh for every
+ * call, NON-ZERO, secret until the verdict is out, and drawn AFTER the commitments and proofs of the batch are fixed.
+ * A predictable or reused rho lets a prover craft a batch that passes the combined check while single proofs fail; the
+ * soundness error is 2^-64 per call.  The host entry rejects rho == 0 (GS_ERR_ARG); the _dev entry cannot look.  The
+ * PPE target is raised WITHOUT a subgroup check.
+ * The host entry stages the four constant arrays once (one copy each) and the four per-proof arrays.  N == 0 is
+ * GS_ERR_ARG; N >= 2^32 is GS_ERR_SHAPE; the entry is refused inside a mixed call (GS_ERR_ARG).  "endo" 0 is followed
+ * as in gs_verify_batch_rlc; "miller_ch" and "line_tables" act as there, "var_tm" forces the terms per Straus lane of
+ * its passes.  The multi-GPU handles (gs_multi_*) have NO counterpart, and there is no fault localisation: a failing
+ * batch goes to gs_verify_batch_rlc_locate with the constants replicated.
+ * WHEN TO CALL IT (tools/eq_rlc_rate.py, profiles/eq_rlc/rate.json, DESIGN.md 6.7: BLS12-381, 4 x 4, one MI355X, device-
+ * resident, median of 7, entries alternating): time of gs_verify_batch_rlc on replicated constants over the time of this
+ * entry at N = 2^12 / 2^14 / 2^16 -- PPE 1.06 / 1.03 / 1.32; QuadEqu 0.77 / 0.98 / 1.16.  A ratio below 1 means
+ * gs_verify_batch_rlc is the faster entry at that size: PPE: at or above parity from 2^12 on; QuadEqu: crossover
+ * between 2^14 and 2^16 (0.98 at 2^14 is inside the spread of that run: treat 2^14 as parity).
+ * Below the crossover call gs_verify_batch_rlc unless replicating the constants is what hurts; above it call this entry.
+ * Kernel profile names: "k_prep_verify_eq_rlc[.shared]", "k_batch_sum.eqs1|.eqs2", "k_miller.eqrlc" (the per-proof
+ * pairs), "k_miller.eqrlc.batch" (the pairs paid once), "k_eq_rlc_tpow". */
+int gs_verify_equation_rlc_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A /* [n] */,
+                               const void* B /* [m] */, const void* Gamma /* [m][n] */, const void* target /* [1] */,
+                               const void* xcoms /* [N][m] */, const void* ycoms /* [N][n] */, const void* pi /* [N][kx] */,
+                               const void* theta /* [N][ky] */, const uint64_t* rho /* [N][4] */, void* acc_gt /* [2] */);
+int gs_verify_equation_rlc(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                           const void* Gamma, const void* target, const void* xcoms, const void* ycoms, const void* pi,
+                           const void* theta, const uint64_t* rho, void* acc_gt /* may be NULL */, uint8_t* ok_all);
 /* product of `count` GT accumulator pairs (host), final exponentiation, FE(prod acc[0]) == prod acc[1] ? */
 int gs_gt_finalize(gs_ctx*, size_t count, const void* accs_gt_host, uint8_t* ok_all);
 /* the same with the pairs in this context's device memory (e.g. the receive buffer of an all-gather); ok_all on the host */

@@ -527,6 +527,52 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     out.equ_proofs.push_back(np);
     return out;
   }
+
+  // (new) ONE verdict for N CProofs of THIS equation (N showings of a credential, N ballots: what rerandomize produces)
+  // from gs_verify_equation_rlc: the constants cross the ABI once, the random linear combination is taken across the
+  // proofs before pairing.  rho is drawn from `rng`, which must be a CSPRNG (the rho contract of gs_amd.h); a batch with
+  // a false proof passes with probability 2^-64.  Which proofs of a failing batch are bad: gs_verify_batch_rlc_locate.
+  template <class Rng> bool verify_rlc_many(const std::vector<CProof>& com_proofs, const CRS& crs, Rng& rng) const {
+    const size_t N = com_proofs.size();
+    if (N == 0) throw Panic("index out of bounds: empty proof list");
+    const size_t m = com_proofs[0].xcoms.coms.size(), n = com_proofs[0].ycoms.coms.size();
+    if (m == 0 || n == 0) throw Panic("index out of bounds: empty commitment list");
+    check_statement_shape(m, n);
+    const Ctx& cx = *crs.ctx;
+    const size_t sx = is_scalar<A1>::value ? cx.sz[1] : cx.sz[2], sy = is_scalar<A2>::value ? cx.sz[1] : cx.sz[3];
+    const size_t tsz = TYPE == EquType::PairingProduct ? cx.sz[4] : TYPE == EquType::MultiScalarG1 ? cx.sz[2]
+                       : TYPE == EquType::MultiScalarG2 ? cx.sz[3] : cx.sz[1];
+    assert_eq(target.v.size(), tsz, "target size");
+    Bytes A = cat(a_consts), B = cat(b_consts), G = cat(gamma), xc, yc, pi, th;
+    assert_eq(A.size(), n * sx, "a_consts bytes");
+    assert_eq(B.size(), m * sy, "b_consts bytes");
+    assert_eq(G.size(), m * n * cx.sz[1], "gamma bytes");
+    for (const CProof& cp : com_proofs) {
+      assert_eq(cp.equ_proofs.size(), 1, "com_proof.equ_proofs.len() == 1");
+      if (cp.equ_proofs[0].equ_type != TYPE) throw Panic("assertion failed: equation type matches the proof's");
+      assert_eq(cp.xcoms.coms.size(), m, "xcoms.len()");
+      assert_eq(cp.ycoms.coms.size(), n, "ycoms.len()");
+      assert_eq(cp.equ_proofs[0].pi.size(), KX, "pi.len()");
+      assert_eq(cp.equ_proofs[0].theta.size(), KY, "theta.len()");
+      Bytes a = cat(cp.xcoms.coms), b = cat(cp.ycoms.coms), p = cat(cp.equ_proofs[0].pi), t = cat(cp.equ_proofs[0].theta);
+      assert_eq(a.size(), m * 2 * cx.sz[2], "xcoms bytes");
+      assert_eq(b.size(), n * 2 * cx.sz[3], "ycoms bytes");
+      assert_eq(p.size(), KX * 2 * cx.sz[3], "pi bytes");
+      assert_eq(t.size(), KY * 2 * cx.sz[2], "theta bytes");
+      xc.insert(xc.end(), a.begin(), a.end());
+      yc.insert(yc.end(), b.begin(), b.end());
+      pi.insert(pi.end(), p.begin(), p.end());
+      th.insert(th.end(), t.begin(), t.end());
+    }
+    std::vector<uint64_t> rho(4 * N);
+    for (auto& v : rho)
+      do v = detail::draw_u64(rng, 0);
+      while (v == 0);
+    uint8_t ok = 0;
+    cx.chk(gs_verify_equation_rlc(cx.c, (int)TYPE, N, (int)m, (int)n, A.data(), B.data(), G.data(), target.v.data(),
+                                  xc.data(), yc.data(), pi.data(), th.data(), rho.data(), nullptr, &ok));
+    return ok == 1;
+  }
 };
 
 using PPE = Equation<G1Affine, G2Affine, GT, EquType::PairingProduct>;
