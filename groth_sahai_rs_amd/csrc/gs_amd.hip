@@ -1072,6 +1072,60 @@ static void add_pair(std::vector<PairRef>& v, int p_arr, int p_idx, int neg, int
   r.pad = 0;
   v.push_back(r);
 }
+// The Miller pairs of a verification equation, stated as FAMILIES of pairs (P_e, Q_e), e < count, between two sites.
+// A site is element `el` onwards of array `arr`: Com-shaped (component c of element e is point 2 e + c) or bare points.
+struct PairSite {
+  int arr, el;
+  bool com = true;
+};
+struct PairFamily {
+  PairSite P, Q;
+  int count;  // 0: the family is absent
+  int neg;    // pair -P
+};
+// Appends (P_e.pc, Q_e.qc) for every family, in list order (the order fixes the task tables and which pairs share a
+// lane).  A bare Q stands for iota(Q) = (O, Q): it only meets component 1.
+static void add_pairs(std::vector<PairRef>& v, std::initializer_list<PairFamily> fams, int pc, int qc) {
+  for (const PairFamily& f : fams) {
+    if (!f.Q.com && qc != 1) continue;
+    for (int e = 0; e < f.count; e++)
+      add_pair(v, f.P.arr, 2 * (f.P.el + e) + pc, f.neg, f.Q.arr, f.Q.com ? 2 * (f.Q.el + e) + qc : f.Q.el + e);
+  }
+}
+// An equation's shape: type and arity, and what the type says about each side (group-valued variables have two columns
+// of commit randomness and two proof elements on the other side, scalars one)
+struct Shape {
+  int ty, m, n;
+  bool xg, yg;
+  int kx, ky;
+  Shape(int ty_, int m_, int n_)
+      : ty(ty_), m(m_), n(n_), xg(x_is_group(ty_)), yg(y_is_group(ty_)), kx(xg ? 2 : 1), ky(yg ? 2 : 1) {}
+};
+// What every verifier is given: the shape, the batch size (statements, for the Statement verifier) and the eight input
+// arrays, in the order of the slots VI_A .. VI_TH
+struct VerifyIn {
+  Shape sh;
+  size_t N;
+  const void *A, *B, *G, *target, *xcoms, *ycoms, *pi, *theta;
+  VerifyIn(int ty, size_t N_, int m, int n, const void* const* p)
+      : sh(ty, m, n), N(N_), A(p[VI_A]), B(p[VI_B]), G(p[VI_G]), target(p[VI_TG]), xcoms(p[VI_XC]), ycoms(p[VI_YC]),
+        pi(p[VI_PI]), theta(p[VI_TH]) {}
+};
+// A pool layout from its fields in pool order: pool_layout({{&PoolMap::GC, m * n}, ...}).  Fields that are not named
+// stay zero.
+struct PoolField {
+  int PoolMap::*field;
+  int count;
+};
+static PoolMap pool_layout(std::initializer_list<PoolField> fields) {
+  PoolMap pm;
+  memset(&pm, 0, sizeof pm);
+  for (const PoolField& f : fields) {
+    pm.*f.field = pm.total;
+    pm.total += f.count;
+  }
+  return pm;
+}
 // An array table in one expression: arr_tab({{i, base, bytes per equation[, present]}, ...}).  Entries that are not
 // named, or not present, stay zero.
 struct ArrEnt {
@@ -1150,6 +1204,45 @@ struct ComOutputs {
     sp.nslots = slot;
   }
 };
+// ---- the G1 outputs of the verifiers, component b.  `pm` is the pool the lanes read: GC Gamma (m x n), BC b (m), and
+// for the batched verifiers RH rho_ab at RH + 2 a + b, AR a_j rho_ab at AR + 4 j + 2 a + b, NR -t rho_ab likewise.
+// sum_i s_i C_i.comp: scalars s0, s0 + stride, ..., the m Com-shaped elements of array `arr` (Gamma's column j, or b)
+static void com_terms(std::vector<VarTask>& t, int s0, int stride, int m, int arr, int comp) {
+  for (int i = 0; i < m; i++) t.push_back(mkvar(s0 + i * stride, arr, 2 * i + comp, 0));
+}
+// rho_0b K.0 + rho_1b K.1 for a CRS element K with tables t0, t1; the scalars (rho, a_j rho, -t rho) start at X
+static void rho_fix(ComOutputs& o, int X, int b, int t0, int t1) { o.fix(X + b, t0, X + 2 + b, t1, 0xFF, 0); }
+// rho_0b E.0 + rho_1b E.1 for element `idx` of array `arr` (C'_i from c_i, Th'_l from theta_l)
+static void rho_comb(ComOutputs& o, const PoolMap& pm, int b, int arr, int idx) {
+  o.terms({mkvar(pm.RH + b, arr, 2 * idx, 0), mkvar(pm.RH + 2 + b, arr, 2 * idx + 1, 0)});
+}
+// P'_j's head: rho_1b A_j (A = array arrA) as a term, or sum_a a_j rho_ab W1.a as a fixed-base lane
+static void head_terms(ComOutputs& o, std::vector<VarTask>& t, const PoolMap& pm, const Shape& s, int j, int b, int arrA) {
+  if (s.xg)
+    t.push_back(mkvar(pm.RH + 2 + b, arrA, j, 0));
+  else
+    rho_fix(o, pm.AR + j * 4, b, tb_w(0), tb_w(1));
+}
+// PB'_b = sum_i b_i C'_ib [- rho_1b t] [- sum_a t rho_ab W1.a]  (C' = array arrC, t = array arrT)
+static void emit_PB(ComOutputs& o, const PoolMap& pm, const Shape& s, int b, int arrC, int arrT) {
+  std::vector<VarTask> terms;
+  com_terms(terms, pm.BC, 1, s.m, arrC, b);
+  if (s.ty == GS_MSMEG1) {
+    VarTask v = mkvar(pm.RH + 2 + b, arrT, 0, 0);
+    v.neg = 1;
+    terms.push_back(v);
+  }
+  if (s.ty == GS_QUAD) rho_fix(o, pm.NR, b, tb_w(0), tb_w(1));
+  o.terms(terms);
+}
+// U'_kb = rho_0b u_k.0 + rho_1b u_k.1 and W1'_b = rho_0b W1.0 + rho_1b W1.1
+static void emit_U(ComOutputs& o, const PoolMap& pm, int k, int b) { rho_fix(o, pm.RH, b, tb_u(k, 0), tb_u(k, 1)); }
+static void emit_W1(ComOutputs& o, const PoolMap& pm, int b) { rho_fix(o, pm.RH, b, tb_w(0), tb_w(1)); }
+// one lane per final exponentiation once `items` of them fill the chip, 3-lane groups (21 per wave) below that
+// (items: the launch's own count, or fillN of it where the launch can be a part of a mixed call)
+static bool coop_lanes(const gs_ctx* c, size_t items) {
+  return c->coop_fe == 2 || (c->coop_fe == 1 && (items + 20) / 21 <= c->simd_slots);
+}
 // Lane cost of the joint MSM in Fq multiplications: one table build of `nt` bases (2^(w-1) entries each: doublings,
 // mixed additions, 7 multiplications per entry for the common denominator) + `no` main loops (w doublings per window,
 // one mixed addition per non-zero digit, the endomorphism on the looked-up entry).
@@ -1671,21 +1764,9 @@ template <class C> struct Impl {
   }
 
   static PoolMap prove_pool(int m, int n, int kx, int ky) {
-    PoolMap pm;
-    memset(&pm, 0, sizeof pm);
-    int o = 0;
-    pm.RC = o; o += m * kx;
-    pm.SC = o; o += n * ky;
-    pm.PSI = o; o += kx * n;
-    pm.PHI = o; o += ky * m;
-    pm.OM = o; o += kx * ky;
-    pm.TC = o; o += ky * kx;
-    pm.RHO = o; o += kx;
-    pm.SIG = o; o += ky;
-    pm.XC = o; o += m;
-    pm.YC = o; o += n;
-    pm.total = o;
-    return pm;
+    return pool_layout({{&PoolMap::RC, m * kx}, {&PoolMap::SC, n * ky}, {&PoolMap::PSI, kx * n}, {&PoolMap::PHI, ky * m},
+                        {&PoolMap::OM, kx * ky}, {&PoolMap::TC, ky * kx}, {&PoolMap::RHO, kx}, {&PoolMap::SIG, ky},
+                        {&PoolMap::XC, m}, {&PoolMap::YC, n}});
   }
 
   // The prover's scalar preparation into `pool`, launched as `name` (large arities: `name`.a and .b, one lane per
@@ -1714,17 +1795,16 @@ template <class C> struct Impl {
   static int prove(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A,
                    const void* B, const void* G, const void* R, const void* Sm, const void* T, void* xcoms,
                    void* ycoms, void* pi, void* theta, bool shared = false) {
-    bool xg = x_is_group(ty), yg = y_is_group(ty);
-    int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
-    PoolMap pm = prove_pool(m, n, kx, ky);
+    const Shape sh(ty, m, n);
+    PoolMap pm = prove_pool(m, n, sh.kx, sh.ky);
     void* pool;
     RC(scratch(c, "prove.pool", N * pm.total * sizeof(S), &pool));
     RangeGuard rg_all("gs.prove");
     // (host-pointer calls: the scalars first; group-valued variables and constants are not read before their side)
-    RC(need(c, BIT(PI_G) | BIT(PI_R) | BIT(PI_S) | BIT(PI_T) | (xg ? 0u : BIT(PI_X) | BIT(PI_A)) |
-                   (yg ? 0u : BIT(PI_Y) | BIT(PI_B))));
-    RC(prep_prove(c, "k_prep_prove", N, m, n, kx, ky, G, R, Sm, T, xg ? nullptr : X, yg ? nullptr : Y, xg ? nullptr : A,
-                  yg ? nullptr : B, pm, pool, shared));
+    RC(need(c, BIT(PI_G) | BIT(PI_R) | BIT(PI_S) | BIT(PI_T) | (sh.xg ? 0u : BIT(PI_X) | BIT(PI_A)) |
+                   (sh.yg ? 0u : BIT(PI_Y) | BIT(PI_B))));
+    RC(prep_prove(c, "k_prep_prove", N, m, n, sh.kx, sh.ky, G, R, Sm, T, sh.xg ? nullptr : X, sh.yg ? nullptr : Y,
+                  sh.xg ? nullptr : A, sh.yg ? nullptr : B, pm, pool, shared));
     // small batches: G1 side on the context's stream, G2 side on side[0], each side's variable-base kernel on a
     // further stream; everything joins back before this function returns
     struct CurGuard {
@@ -1745,8 +1825,8 @@ template <class C> struct Impl {
     auto side = [&](auto* ftag) -> int {
       typedef std::remove_pointer_t<decltype(ftag)> F;
       constexpr bool g2 = std::is_same<F, F2>::value;
-      const bool grp = g2 ? yg : xg;
-      const int nv = g2 ? n : m, nc = g2 ? m : n, kc = g2 ? ky : kx, npf = g2 ? kx : ky;
+      const bool grp = g2 ? sh.yg : sh.xg;
+      const int nv = g2 ? n : m, nc = g2 ? m : n, kc = g2 ? sh.ky : sh.kx, npf = g2 ? sh.kx : sh.ky;
       const size_t zp = g2 ? Z::G2 : Z::G1;
       void* coms = g2 ? ycoms : xcoms;
       SidePlan sp;
@@ -1795,21 +1875,21 @@ template <class C> struct Impl {
   static int rerandomize(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
                          const void* xc, const void* yc, const void* pi, const void* th, const void* R, const void* Sm,
                          const void* T, void* xco, void* yco, void* pio, void* tho, bool shared) {
-    bool xg = x_is_group(ty), yg = y_is_group(ty);
-    int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
-    PoolMap pm = prove_pool(m, n, kx, ky);
+    const Shape sh(ty, m, n);
+    PoolMap pm = prove_pool(m, n, sh.kx, sh.ky);
     void* pool;
     RC(scratch(c, "rerand.pool", N * pm.total * sizeof(S), &pool));
     RangeGuard rg_all("gs.rerandomize");
-    RC(need(c, BIT(RI_G) | BIT(RI_R) | BIT(RI_S) | BIT(RI_T) | (xg ? 0u : BIT(RI_A)) | (yg ? 0u : BIT(RI_B))));
-    RC(prep_prove(c, "k_prep_rerand", N, m, n, kx, ky, G, R, Sm, T, nullptr, nullptr, xg ? nullptr : A, yg ? nullptr : B,
-                  pm, pool, shared));
+    RC(need(c, BIT(RI_G) | BIT(RI_R) | BIT(RI_S) | BIT(RI_T) | (sh.xg ? 0u : BIT(RI_A)) | (sh.yg ? 0u : BIT(RI_B))));
+    RC(prep_prove(c, "k_prep_rerand", N, m, n, sh.kx, sh.ky, G, R, Sm, T, nullptr, nullptr, sh.xg ? nullptr : A,
+                  sh.yg ? nullptr : B, pm, pool, shared));
     // one side over NN equations: the commitments (coms) and / or the proof elements (proofs) of that side
     auto side = [&](auto* ftag, size_t NN, bool coms, bool proofs, const char* tag) -> int {
       typedef std::remove_pointer_t<decltype(ftag)> F;
       constexpr bool g2 = std::is_same<F, F2>::value;
-      const bool grp = g2 ? yg : xg;
-      const int nv = g2 ? n : m, nc = g2 ? m : n, kc = g2 ? ky : kx, npf = g2 ? kx : ky, np = proofs ? npf : 0;
+      const bool grp = g2 ? sh.yg : sh.xg;
+      const int nv = g2 ? n : m, nc = g2 ? m : n, kc = g2 ? sh.ky : sh.kx, npf = g2 ? sh.kx : sh.ky,
+                np = proofs ? npf : 0;
       const uint32_t zp = (uint32_t)(g2 ? Z::G2 : Z::G1);
       SidePlan sp;
       sp.tm = np ? pick_tm(c, fillN(c, NN), grp ? nv + nc : nv, 2 * np, g2, np) : 1;
@@ -1850,11 +1930,7 @@ template <class C> struct Impl {
                     const Aff<F>* tab, const char* tag) {
     int kc = group ? 2 : 1;
     const size_t bsz = sizeof(Aff<F>) == sizeof(A1) ? Z::G1 : Z::G2;  // boundary bytes of one point
-    PoolMap pm;
-    memset(&pm, 0, sizeof pm);
-    pm.RC = 0;
-    pm.XC = kc;
-    pm.total = kc + 1;
+    const PoolMap pm = pool_layout({{&PoolMap::RC, kc}, {&PoolMap::XC, 1}});
     void* pool;
     RC(scratch(c, "commit.pool", count * pm.total * sizeof(S), &pool));
     // reuse k_prep_prove with m = 1 variable per "equation", no Gamma work (n = 0, ky = 0)
@@ -1876,15 +1952,8 @@ template <class C> struct Impl {
     int npa;                          // Com1 elements in the PA scratch per equation
   };
 
-  // P arrays: 0 PA scratch, 1 xcoms, 2 crs G1 consts, 3 theta
-  // Q arrays: 0 ycoms, 1 B, 2 crs G2 consts, 3 pi, 4 target (MSMEG2)
-  static void build_verify(VerifyPlan& vp, int curve, int ty, int m, int n, const PoolMap& pm, double budget, bool twin,
-                           int tm, bool lt) {
-    build_verify_g1(vp, ty, m, n, pm, tm);
-    build_verify_miller(vp, curve, ty, m, n, budget, twin, lt);
-  }
-  static void build_verify_g1(VerifyPlan& vp, int ty, int m, int n, const PoolMap& pm, int tm) {
-    bool xg = x_is_group(ty), yg = y_is_group(ty);
+  static void build_verify_g1(VerifyPlan& vp, const Shape& s, const PoolMap& pm, int tm) {
+    const int m = s.m, n = s.n;
     // ---- G1-side points: PA_j.a = map_a_j.a + sum_i Gamma_ij c_i.a ;  PB.a = sum_i b_i c_i.a - lin_t
     // engine arrays: 0 = xcoms as 2m G1 points, 1 = A (group), 2 = target (MSMEG1)
     SidePlan& sp = vp.g1;
@@ -1895,29 +1964,29 @@ template <class C> struct Impl {
     }
     ComOutputs out{sp};
     out.add(n, 0, 0, [&](int j, int a, ComOutputs& o) {
-      if (!xg)
+      if (!s.xg)
         o.fix(pm.AC + j, tb_w(a), 0, 0xFF, 0xFF, 0);
       else if (a == 1)
         o.fix(0, 0xFF, 0, 0xFF, 1, j);
       std::vector<VarTask> terms;
-      for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, 2 * i + a, 0));
+      com_terms(terms, pm.GC + j, n, m, 0, a);
       o.terms(terms);
     });
     vp.npa = n;
-    if (!yg) {
+    if (!s.yg) {
       out.add(1, 0, n, [&](int, int a, ComOutputs& o) {
         std::vector<VarTask> terms;
-        for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.BC + i, 0, 2 * i + a, 0));
+        com_terms(terms, pm.BC, 1, m, 0, a);
         o.terms(terms);
-        if (ty == GS_MSMEG1 && a == 1) o.fix(0, 0xFF, 0, 0xFF, 2, 0, 1);  // - t
-        if (ty == GS_QUAD) o.fix(pm.NT, tb_w(a), 0, 0xFF, 0xFF, 0);       // (-t) W1.a
+        if (s.ty == GS_MSMEG1 && a == 1) o.fix(0, 0xFF, 0, 0xFF, 2, 0, 1);  // - t
+        if (s.ty == GS_QUAD) o.fix(pm.NT, tb_w(a), 0, 0xFF, 0xFF, 0);       // (-t) W1.a
       });
       vp.npa = n + 1;
     }
   }
-  static void build_verify_miller(VerifyPlan& vp, int curve, int ty, int m, int n, double budget, bool twin, bool lt) {
-    bool xg = x_is_group(ty), yg = y_is_group(ty);
-    int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
+  // P arrays: 0 PA scratch, 1 xcoms, 2 crs G1 consts, 3 theta
+  // Q arrays: 0 ycoms, 1 B, 2 crs G2 consts, 3 pi, 4 target (MSMEG2)
+  static void build_verify_miller(VerifyPlan& vp, int curve, const Shape& s, double budget, bool twin, bool lt) {
     // ---- Miller tasks.  Pairs of cell (a, b): G1 argument = component a, G2 argument = component b.
     //  twin  : one task list per b, each lane takes `ch` (Q, P0, P1) triples and keeps two accumulators
     //          (lines of Q computed once) -- less total work, pays off once the chip is full;
@@ -1926,16 +1995,14 @@ template <class C> struct Impl {
     for (int cell = 0; cell < (twin ? 2 : 4); cell++) {
       int b = twin ? cell : (cell & 1), a = twin ? 0 : (cell >> 1);
       std::vector<PairRef> pr;
-      for (int j = 0; j < n; j++) add_pair(pr, 0, 2 * j + a, 0, 0, 2 * j + b);      // (PA_j.a, d_j.b)
-      if (yg) {
-        if (b == 1)
-          for (int i = 0; i < m; i++) add_pair(pr, 1, 2 * i + a, 0, 1, i);          // (c_i.a, B_i)
-      } else {
-        add_pair(pr, 0, 2 * n + a, 0, 2, 4 + b);                                    // (PB.a, W2.b)
-      }
-      for (int k = 0; k < kx; k++) add_pair(pr, 2, 2 * k + a, 1, 3, 2 * k + b);     // (-u_k.a, pi_k.b)
-      for (int l = 0; l < ky; l++) add_pair(pr, 3, 2 * l + a, 1, 2, 2 * l + b);     // (-theta_l.a, v_l.b)
-      if (ty == GS_MSMEG2 && b == 1) add_pair(pr, 2, 4 + a, 1, 4, 0);               // (-W1.a, t)
+      add_pairs(pr,
+                {{{0, 0}, {0, 0}, s.n, 0},                          // (PA_j, d_j)
+                 {{1, 0}, {1, 0, false}, s.yg ? s.m : 0, 0},        // (c_i, B_i)
+                 {{0, s.n}, {2, 2}, s.yg ? 0 : 1, 0},               // (PB, W2)
+                 {{2, 0}, {3, 0}, s.kx, 1},                         // (-u_k, pi_k)
+                 {{3, 0}, {2, 0}, s.ky, 1},                         // (-theta_l, v_l)
+                 {{2, 2}, {4, 0, false}, s.ty == GS_MSMEG2, 1}},    // (-W1, t)
+                a, b);
       int lo = (int)vp.mt.size();
       chunk_tasks(vp.mt, pr, budget, b, !twin, mcost(curve, twin), lt);
       int hi = (int)vp.mt.size();
@@ -1977,27 +2044,29 @@ template <class C> struct Impl {
               (GT*)*mpart, 1, lines(c));
   }
 
+  // Q arrays of the exact verifier and of rlc_front: 0 ycoms, 1 B, 2 crs G2 consts, 3 pi, 4 target (MSMEG2)
+  // (shared: a Statement's equations share the commitments)
+  static ArrTab q_arrays(const gs_ctx* c, const VerifyIn& v, bool shared) {
+    return arr_tab({{0, v.ycoms, shared ? 0u : (uint32_t)(v.sh.n * Z::COM2)},
+                    {1, v.B, (uint32_t)(v.sh.m * Z::G2)},
+                    {2, c->tabs->crs_g2.p, 0},
+                    {3, v.pi, (uint32_t)(v.sh.kx * Z::COM2)},
+                    {4, v.target, (uint32_t)Z::G2}});
+  }
+
   // shared front of both verifier modes: G1-side points + Miller partials
-  static int verify_front(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                          const void* target, const void* xcoms, const void* ycoms, const void* pi,
-                          const void* theta, VerifyPlan& vp, void** mpart_out, bool shared = false) {
-    bool xg = x_is_group(ty), yg = y_is_group(ty);
-    int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
-    PoolMap pm;
-    memset(&pm, 0, sizeof pm);
-    int o = 0;
-    pm.GC = o; o += m * n;
-    pm.AC = o; o += n;
-    pm.BC = o; o += m;
-    pm.NT = o; o += 1;
-    pm.total = o;
+  static int verify_front(gs_ctx* c, const VerifyIn& v, VerifyPlan& vp, void** mpart_out, bool shared) {
+    const Shape& s = v.sh;
+    const int ty = s.ty, m = s.m, n = s.n;
+    const size_t N = v.N;
+    const PoolMap pm = pool_layout({{&PoolMap::GC, m * n}, {&PoolMap::AC, n}, {&PoolMap::BC, m}, {&PoolMap::NT, 1}});
     void* pool;
     RC(scratch(c, "verify.pool", N * pm.total * sizeof(S), &pool));
-    RC(need(c, BIT(VI_G) | (xg ? 0u : BIT(VI_A)) | (yg ? 0u : BIT(VI_B)) | (ty == GS_QUAD ? BIT(VI_TG) : 0u)));
+    RC(need(c, BIT(VI_G) | (s.xg ? 0u : BIT(VI_A)) | (s.yg ? 0u : BIT(VI_B)) | (ty == GS_QUAD ? BIT(VI_TG) : 0u)));
     const S* g;
-    RC(prep_gamma(c, N, m, n, G, pm, pool, &g));
-    RC(launch_seg<k_prep_verify<C>>(c, "k_prep_verify", N, 64, N, m, n, g, xg ? nullptr : (const S*)A,
-              yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, pm, (S*)pool));
+    RC(prep_gamma(c, N, m, n, v.G, pm, pool, &g));
+    RC(launch_seg<k_prep_verify<C>>(c, "k_prep_verify", N, 64, N, m, n, g, s.xg ? nullptr : (const S*)v.A,
+              s.yg ? nullptr : (const S*)v.B, ty == GS_QUAD ? (const S*)v.target : nullptr, pm, (S*)pool));
     // lane shape for this batch size: single or twin accumulators (the twin task list on one lane with two
     // accumulators, or on a pair of lanes with one each), lane-cost budget (cost model above)
     int mode = 0;  // 0 single, 1 twin, 2 pair (LDS exchange), 3 pair (DPP exchange)
@@ -2018,7 +2087,7 @@ template <class C> struct Impl {
           if (c->miller_twin < 0 && md == 2 && !GS_PLAN_PAIR) continue;
           for (double cand : miller_budgets(c, md != 0)) {
             VerifyPlan tmp;
-            build_verify_miller(tmp, c->curve, ty, m, n, cand, md != 0, c->line_tables);
+            build_verify_miller(tmp, c->curve, s, cand, md != 0, c->line_tables);
             double cost = miller_cost(c, NF, tmp.mt, md != 0, md == 2);
             if (md == 2) cost *= 0.97;  // measured: the same triples finish 3-4 % sooner with one accumulator per lane
             if (best < 0 || cost < best) {
@@ -2044,16 +2113,16 @@ template <class C> struct Impl {
     const double tab8_bytes = (double)N * 2.0 * m * 128.0 * (double)(sizeof(A1) + sizeof(Jac<F1>));
     // (the shared base tables are read by endomorphism-decomposed lanes: not with "endo" off)
     const bool tab8 = c->endo && (c->var_tab == 1 || (c->var_tab < 0 && wide_prep(m, n) && n >= 32 && tab8_bytes <= 8e9));
-    build_verify(vp, c->curve, ty, m, n, pm, budget, twin, tab8 ? -1 : pick_tm(c, fillN(c, N), m, 2 * n, false, n),
-                 c->line_tables);
+    build_verify_g1(vp, s, pm, tab8 ? -1 : pick_tm(c, fillN(c, N), m, 2 * n, false, n));
+    build_verify_miller(vp, c->curve, s, budget, twin, c->line_tables);
     // G1-side points
     void* pa;
     RC(scratch(c, "verify.pa", N * vp.npa * Z::COM1, &pa));
     {
       // (a Statement's equations share the commitments)
-      const ArrTab arrs = arr_tab({{0, xcoms, shared ? 0u : (uint32_t)(m * Z::COM1)},
-                                   {1, A, (uint32_t)(n * Z::G1), xg},
-                                   {2, target, (uint32_t)Z::G1, ty == GS_MSMEG1}});
+      const ArrTab arrs = arr_tab({{0, v.xcoms, shared ? 0u : (uint32_t)(m * Z::COM1)},
+                                   {1, v.A, (uint32_t)(n * Z::G1), s.xg},
+                                   {2, v.target, (uint32_t)Z::G1, ty == GS_MSMEG1}});
       const OutTab outs = out_tab(pa, (uint32_t)(vp.npa * Z::COM1));
       RangeGuard rg("gs.verify.g1");
       RC(need(c, BIT(VI_XC) | BIT(VI_A) | BIT(VI_TG) * (ty == GS_MSMEG1 ? 1u : 0u)));
@@ -2068,14 +2137,10 @@ template <class C> struct Impl {
     void* mpart;
     RC(scratch(c, "verify.mpart", 2 * N * ntask * sizeof(GT), &mpart));
     const ArrTab parr = arr_tab({{0, pa, (uint32_t)(vp.npa * Z::COM1)},
-                                 {1, xcoms, shared ? 0u : (uint32_t)(m * Z::COM1)},
+                                 {1, v.xcoms, shared ? 0u : (uint32_t)(m * Z::COM1)},
                                  {2, c->tabs->crs_g1.p, 0},
-                                 {3, theta, (uint32_t)(ky * Z::COM1)}});
-    const ArrTab qarr = arr_tab({{0, ycoms, shared ? 0u : (uint32_t)(n * Z::COM2)},
-                                 {1, B, (uint32_t)(m * Z::G2)},
-                                 {2, c->tabs->crs_g2.p, 0},
-                                 {3, pi, (uint32_t)(kx * Z::COM2)},
-                                 {4, target, (uint32_t)Z::G2}});
+                                 {3, v.theta, (uint32_t)(s.ky * Z::COM1)}});
+    const ArrTab qarr = q_arrays(c, v, shared);
     miller_work_hint(c, N, vp.mt, twin);
     if (getenv("GS_PLAN_TRACE")) {
       const MCost mc = mcost(c->curve, twin);
@@ -2104,13 +2169,13 @@ template <class C> struct Impl {
     return GS_OK;
   }
 
-  static int verify(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                    const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                    uint8_t* ok, bool shared = false) {
+  static int verify(gs_ctx* c, const VerifyIn& v, uint8_t* ok, bool shared) {
+    const size_t N = v.N;
+    const uint8_t* target = v.sh.ty == GS_PPE ? (const uint8_t*)v.target : nullptr;
     VerifyPlan vp;
     void* mpart;
     RangeGuard rg_all("gs.verify");
-    RC(verify_front(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, vp, &mpart, shared));
+    RC(verify_front(c, v, vp, &mpart, shared));
     RangeGuard rg_f("gs.verify.final");
     int ntask = (int)vp.mt.size();
     // large arities: hundreds of Miller partials per cell -- fold runs of K in parallel until k_final's own serial
@@ -2142,14 +2207,11 @@ template <class C> struct Impl {
     }
     void* cellok;
     RC(scratch(c, "verify.cellok", N * 4, &cellok));
-    // one lane per final exponentiation once that fills the chip, 3-lane groups (21 per wave) below that
-    size_t coop_waves = (N * 4 + 20) / 21;
-    if (c->coop_fe == 2 || (c->coop_fe == 1 && (fillN(c, N) * 4 + 20) / 21 <= c->simd_slots))
-      RC(launch_seg<k_final_coop<C>>(c, "k_final.coop", coop_waves * 63, 63, N, ntask, cm, (const GT*)mpart,
-                ty == GS_PPE ? (const uint8_t*)target : nullptr, (uint8_t*)cellok));
+    if (coop_lanes(c, fillN(c, N) * 4))
+      RC(launch_seg<k_final_coop<C>>(c, "k_final.coop", (N * 4 + 20) / 21 * 63, 63, N, ntask, cm, (const GT*)mpart, target,
+                (uint8_t*)cellok));
     else
-      RC(launch_seg<k_final<C>>(c, "k_final", N * 4, 64, N, ntask, cm,
-                (const GT*)mpart, ty == GS_PPE ? (const uint8_t*)target : nullptr, (uint8_t*)cellok));
+      RC(launch_seg<k_final<C>>(c, "k_final", N * 4, 64, N, ntask, cm, (const GT*)mpart, target, (uint8_t*)cellok));
     RC(launch_seg<k_and4>(c, "k_and4", N, 64, N, (const uint8_t*)cellok, ok));
     return GS_OK;
   }
@@ -2181,122 +2243,90 @@ template <class C> struct Impl {
   //   2. P'_jb = rho_1b A_j + sum_i Gamma_ij C'_ib   (a_j rho_ab W1.a for scalar constants),
   //      PB'_b, U'_kb = rho_0b u_k.0 + rho_1b u_k.1, W1'_b      (Com-shaped: components b = 0, 1)
   // rlc_front: the pool, both G1 passes and the Miller launch; leaves N * ntask partials, equation-major, in rlc.mpart
-  static int rlc_front(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                       const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                       const uint64_t* rho, void** mpart, int* ntask_out) {
-    bool xg = x_is_group(ty), yg = y_is_group(ty);
-    int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
-    PoolMap pm;
-    memset(&pm, 0, sizeof pm);
-    int o = 0;
-    pm.GC = o; o += m * n;
-    pm.BC = o; o += m;
-    pm.RH = o; o += 4;
-    pm.AR = o; o += 4 * n;
-    pm.NR = o; o += 4;
-    pm.total = o;
+  static int rlc_front(gs_ctx* c, const VerifyIn& v, const uint64_t* rho, void** mpart, int* ntask_out) {
+    const Shape& s = v.sh;
+    const int ty = s.ty, m = s.m, n = s.n;
+    const size_t N = v.N;
+    const PoolMap pm = pool_layout({{&PoolMap::GC, m * n}, {&PoolMap::BC, m}, {&PoolMap::RH, 4}, {&PoolMap::AR, 4 * n},
+                                    {&PoolMap::NR, 4}});
     void* pool;
     RC(scratch(c, "rlc.pool", N * pm.total * sizeof(S), &pool));
     const S* g;
-    RC(prep_gamma(c, N, m, n, G, pm, pool, &g));
-    RC(launch(c, "k_prep_verify_rlc", k_prep_verify_rlc<C>, N, 64, N, m, n, g, xg ? nullptr : (const S*)A,
-              yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, rho, pm, (S*)pool));
-    auto RH = [&](int a, int b) { return pm.RH + 2 * a + b; };
-    // ---- pass 1
-    int n1 = m + ky;
+    RC(prep_gamma(c, N, m, n, v.G, pm, pool, &g));
+    RC(launch(c, "k_prep_verify_rlc", k_prep_verify_rlc<C>, N, 64, N, m, n, g, s.xg ? nullptr : (const S*)v.A,
+              s.yg ? nullptr : (const S*)v.B, ty == GS_QUAD ? (const S*)v.target : nullptr, rho, pm, (S*)pool));
+    // ---- pass 1: C'_i from xcoms (array 0), Th'_l from theta (array 1)
+    int n1 = m + s.ky;
     void* s1;
     RC(scratch(c, "rlc.s1", N * n1 * Z::COM1, &s1));
     {
       SidePlan sp;
       sp.tm = c->endo ? 4 : 1;  // endo = 0: one plain double-and-add lane per term ("k_var.plain"), as everywhere else
-      ComOutputs{sp}.add(n1, 0, 0, [&](int q, int b, ComOutputs& o) {
-        int arr = q < m ? 0 : 1, idx = q < m ? q : q - m;
-        o.terms({mkvar(RH(0, b), arr, 2 * idx, 0), mkvar(RH(1, b), arr, 2 * idx + 1, 0)});
-      });
-      const ArrTab arrs = arr_tab({{0, xcoms, (uint32_t)(m * Z::COM1)}, {1, theta, (uint32_t)(ky * Z::COM1)}});
+      ComOutputs{sp}.add(n1, 0, 0,
+                         [&](int q, int b, ComOutputs& o) { rho_comb(o, pm, b, q < m ? 0 : 1, q < m ? q : q - m); });
+      const ArrTab arrs = arr_tab({{0, v.xcoms, (uint32_t)(m * Z::COM1)}, {1, v.theta, (uint32_t)(s.ky * Z::COM1)}});
       const OutTab outs = out_tab(s1, (uint32_t)(n1 * Z::COM1));
       RC((run_side<C, F1>(c, ".r1", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
-    // ---- pass 2: elements 0..n-1 = P'_j, then [PB'] , U'_k (kx), [W1'] (MSMEG2)
-    int iPB = n, iU = n + (yg ? 0 : 1), iW = iU + kx, n2 = iW + (ty == GS_MSMEG2 ? 1 : 0);
+    // ---- pass 2: elements 0..n-1 = P'_j, then [PB'] , U'_k (kx), [W1'] (MSMEG2).  Arrays: 0 = S1, 1 = A, 2 = target
+    int iPB = n, iU = n + (s.yg ? 0 : 1), iW = iU + s.kx, n2 = iW + (ty == GS_MSMEG2 ? 1 : 0);
     void* s2;
     RC(scratch(c, "rlc.s2", N * n2 * Z::COM1, &s2));
     {
       SidePlan sp;
       sp.tm = c->endo ? 8 : 1;
       ComOutputs{sp}.add(n2, 0, 0, [&](int q, int b, ComOutputs& o) {
-        std::vector<VarTask> terms;
         if (q < n) {
-          int j = q;
-          if (xg)
-            terms.push_back(mkvar(RH(1, b), 1, j, 0));                                        // rho_1b A_j
-          else
-            o.fix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0);
-          for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, 2 * i + b, 0));  // Gamma_ij C'_ib
-        } else if (!yg && q == iPB) {
-          for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.BC + i, 0, 2 * i + b, 0));          // b_i C'_ib
-          if (ty == GS_MSMEG1) {
-            VarTask v = mkvar(RH(1, b), 2, 0, 0);                                                  // - rho_1b t
-            v.neg = 1;
-            terms.push_back(v);
-          }
-          if (ty == GS_QUAD) o.fix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0);
-        } else if (q >= iU && q < iU + kx) {
-          int k = q - iU;
-          o.fix(RH(0, b), tb_u(k, 0), RH(1, b), tb_u(k, 1), 0xFF, 0);
-        } else {  // W1' (MSMEG2)
-          o.fix(RH(0, b), tb_w(0), RH(1, b), tb_w(1), 0xFF, 0);
+          std::vector<VarTask> terms;
+          head_terms(o, terms, pm, s, q, b, 1);
+          com_terms(terms, pm.GC + q, n, m, 0, b);  // Gamma_ij C'_ib
+          o.terms(terms);
+        } else if (!s.yg && q == iPB) {
+          emit_PB(o, pm, s, b, 0, 2);
+        } else if (q < iW) {
+          emit_U(o, pm, q - iU, b);
+        } else {  // (MSMEG2)
+          emit_W1(o, pm, b);
         }
-        o.terms(terms);
       });
       const ArrTab arrs = arr_tab({{0, s1, (uint32_t)(n1 * Z::COM1)},
-                                   {1, A, (uint32_t)(n * Z::G1), xg},
-                                   {2, target, (uint32_t)Z::G1, ty == GS_MSMEG1}});
+                                   {1, v.A, (uint32_t)(n * Z::G1), s.xg},
+                                   {2, v.target, (uint32_t)Z::G1, ty == GS_MSMEG1}});
       const OutTab outs = out_tab(s2, (uint32_t)(n2 * Z::COM1));
       RC((run_side<C, F1>(c, ".r2", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
-    // ---- Miller: every G2 argument once.  P arrays: 0 = S2, 1 = S1.  Q arrays: 0 ycoms, 1 B, 2 crs, 3 pi, 4 target
+    // ---- Miller: every G2 argument once.  P arrays: 0 = S2, 1 = S1.  Q arrays: q_arrays
     std::vector<PairRef> pr;
-    for (int b = 0; b < 2; b++) {
-      for (int j = 0; j < n; j++) add_pair(pr, 0, 2 * j + b, 0, 0, 2 * j + b);
-      if (yg) {
-        if (b == 1)
-          for (int i = 0; i < m; i++) add_pair(pr, 1, 2 * i + 1, 0, 1, i);
-      } else {
-        add_pair(pr, 0, 2 * iPB + b, 0, 2, 4 + b);
-      }
-      for (int k = 0; k < kx; k++) add_pair(pr, 0, 2 * (iU + k) + b, 1, 3, 2 * k + b);
-      for (int l = 0; l < ky; l++) add_pair(pr, 1, 2 * (m + l) + b, 1, 2, 2 * l + b);
-      if (ty == GS_MSMEG2 && b == 1) add_pair(pr, 0, 2 * iW + 1, 1, 4, 0);
-    }
+    for (int b = 0; b < 2; b++)
+      add_pairs(pr,
+                {{{0, 0}, {0, 0}, n, 0},                                    // (P'_j, d_j)
+                 {{1, 0}, {1, 0, false}, s.yg ? m : 0, 0},                  // (C'_i, B_i)
+                 {{0, iPB}, {2, 2}, s.yg ? 0 : 1, 0},                       // (PB', W2)
+                 {{0, iU}, {3, 0}, s.kx, 1},                                // (-U'_k, pi_k)
+                 {{1, m}, {2, 0}, s.ky, 1},                                 // (-Th'_l, v_l)
+                 {{0, iW}, {4, 0, false}, ty == GS_MSMEG2 ? 1 : 0, 1}},     // (-W1', t)
+                b, b);
     const ArrTab parr = arr_tab({{0, s2, (uint32_t)(n2 * Z::COM1)}, {1, s1, (uint32_t)(n1 * Z::COM1)}});
-    const ArrTab qarr = arr_tab({{0, ycoms, (uint32_t)(n * Z::COM2)},
-                                 {1, B, (uint32_t)(m * Z::G2)},
-                                 {2, c->tabs->crs_g2.p, 0},
-                                 {3, pi, (uint32_t)(kx * Z::COM2)},
-                                 {4, target, (uint32_t)Z::G2}});
     const std::vector<MillerTask> mt = plan_miller_single(c, N, pr);
     *ntask_out = (int)mt.size();
-    return miller_single(c, "rlc", N, mt, parr, qarr, mpart);
+    return miller_single(c, "rlc", N, mt, parr, q_arrays(c, v, false), mpart);
   }
-  static int verify_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                        const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                        const uint64_t* rho, void* acc) {
+  // acc[1] of a batched check: the product `t` of the targets' powers (PPE) or, with t null, the identity (built in `one`)
+  static int put_acc1(gs_ctx* c, const GT* t, GT* one, void* acc) {
+    if (!t) RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, one));
+    return launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, t ? t : (const GT*)one, (uint8_t*)acc + Z::GT);
+  }
+  static int verify_rlc(gs_ctx* c, const VerifyIn& v, const uint64_t* rho, void* acc) {
+    const size_t N = v.N;
     void *mpart, *pt, *tmp;
     int ntask;
-    RC(rlc_front(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, &mpart, &ntask));
+    RC(rlc_front(c, v, rho, &mpart, &ntask));
     RC(scratch(c, "rlc.t", (N + 1) * sizeof(GT), &pt));
     RC(scratch(c, "rlc.tmp", (N * ntask / 4 + 8) * sizeof(GT), &tmp));
-    uint8_t* a = (uint8_t*)acc;
-    RC(gt_product(c, N * ntask, (GT*)mpart, (GT*)tmp, a));
-    if (ty == GS_PPE) {
-      RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, N, 64, N, (const uint8_t*)target, rho, (GT*)pt));
-      RC(gt_product(c, N, (GT*)pt, (GT*)tmp, a + Z::GT));
-    } else {
-      RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, (GT*)pt));
-      RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)pt, a + Z::GT));
-    }
-    return GS_OK;
+    RC(gt_product(c, N * ntask, (GT*)mpart, (GT*)tmp, (uint8_t*)acc));
+    if (v.sh.ty != GS_PPE) return put_acc1(c, nullptr, (GT*)pt, acc);
+    RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, N, 64, N, (const uint8_t*)v.target, rho, (GT*)pt));
+    return gt_product(c, N, (GT*)pt, (GT*)tmp, (uint8_t*)acc + Z::GT);
   }
 
   // Sum, across the `rows` rows of a device array, of the first `count` Com-shaped elements of every row (group F):
@@ -2346,40 +2376,31 @@ template <class C> struct Impl {
   // Scalars: a pool per proof (rho, a_j rho) and ONE shared pool (Gamma, b, r, -t r), which the per-proof pass over
   // Gamma reads with a pool stride of 0.  So that this pass needs shared scalars only, rho_e,1b A_j (a_j rho_e,ab W1.a)
   // is an output of pass 1 and enters P' as the affine addend of a fixed-base lane without fixed-base terms.
-  static int verify_eq_rlc(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                           const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
-                           const uint64_t* rho, void* acc) {
-    const bool xg = x_is_group(ty), yg = y_is_group(ty);
-    const int kx = xg ? 2 : 1, ky = yg ? 2 : 1;
+  static int verify_eq_rlc(gs_ctx* c, const VerifyIn& v, const uint64_t* rho, void* acc) {
+    const Shape& s = v.sh;
+    const int ty = s.ty, m = s.m, n = s.n, kx = s.kx, ky = s.ky;
+    const bool xg = s.xg, yg = s.yg;
+    const size_t N = v.N;
     // planned: pi per proof, as measured at 2^14 for PPE and QuadEqu; folded in G2 where a proof has two pi elements and
     // the batch has 2^16 proofs or more (the fold is ahead there for PPE; profiles/eq_rlc/rate.json)
     const bool fold_pi = c->eq_pi >= 0 ? c->eq_pi == 1 : (kx == 2 && N >= ((size_t)1 << 16));
     RangeGuard rg_all("gs.verify_eq_rlc");
-    PoolMap pp, ps;  // per proof, shared
-    memset(&pp, 0, sizeof pp);
-    memset(&ps, 0, sizeof ps);
-    pp.RH = 0;
-    pp.AR = 4;
-    pp.total = 4 + (xg ? 0 : 4 * n);
-    ps.GC = 0;
-    ps.BC = m * n;
-    ps.RH = ps.BC + m;
-    ps.NR = ps.RH + 4;
-    ps.total = ps.NR + 4;
+    // per proof, shared
+    const PoolMap pp = pool_layout({{&PoolMap::RH, 4}, {&PoolMap::AR, xg ? 0 : 4 * n}});
+    const PoolMap ps = pool_layout({{&PoolMap::GC, m * n}, {&PoolMap::BC, m}, {&PoolMap::RH, 4}, {&PoolMap::NR, 4}});
     void *pool, *spool, *sums;
     RC(scratch(c, "eqrlc.pool", N * pp.total * sizeof(S), &pool));
     RC(scratch(c, "eqrlc.spool", ps.total * sizeof(S), &spool));
     RC(scratch(c, "eqrlc.sums", 8 * sizeof(unsigned long long), &sums));
     HIPCHK(c, hipMemsetAsync(sums, 0, 8 * sizeof(unsigned long long), c->cur ? c->cur : c->stream));
-    RC(launch(c, "k_prep_verify_eq_rlc", k_prep_verify_eq_rlc<C>, (N + 63) / 64 * 64, 64, N, n, xg ? nullptr : (const S*)A,
-              rho, pp, (S*)pool, (unsigned long long*)sums));
+    RC(launch(c, "k_prep_verify_eq_rlc", k_prep_verify_eq_rlc<C>, (N + 63) / 64 * 64, 64, N, n,
+              xg ? nullptr : (const S*)v.A, rho, pp, (S*)pool, (unsigned long long*)sums));
     {
       const size_t lanes = std::max((size_t)m * n, (size_t)1);
-      RC(launch(c, "k_prep_verify_eq_rlc.shared", k_prep_verify_eq_rlc_shared<C>, lanes, 64, m, n, (const S*)G,
-                yg ? nullptr : (const S*)B, ty == GS_QUAD ? (const S*)target : nullptr, (const unsigned long long*)sums,
-                ps, (S*)spool));
+      RC(launch(c, "k_prep_verify_eq_rlc.shared", k_prep_verify_eq_rlc_shared<C>, lanes, 64, m, n, (const S*)v.G,
+                yg ? nullptr : (const S*)v.B, ty == GS_QUAD ? (const S*)v.target : nullptr,
+                (const unsigned long long*)sums, ps, (S*)spool));
     }
-    auto RH = [&](int a, int b) { return 2 * a + b; };  // + pp.RH (per proof) or ps.RH (the sums)
     // terms per Straus lane: "var_tm" forces it; endo = 0: one plain double-and-add lane per term, as everywhere else
     auto TM = [&](int planned) { return !c->endo ? 1 : c->var_tm > 0 ? c->var_tm : planned; };
     // ---- pass 1 (per proof): C'_i (m), Th'_l (ky), RA_j = rho_1b A_j | sum_a a_j rho_ab W1.a (n), [U'_k (kx)]
@@ -2391,20 +2412,17 @@ template <class C> struct Impl {
       sp.tm = TM(4);
       ComOutputs{sp}.add(n1, 0, 0, [&](int q, int b, ComOutputs& o) {
         if (q < iRA) {
-          const int arr = q < m ? 0 : 1, idx = q < m ? q : q - m;
-          o.terms({mkvar(pp.RH + RH(0, b), arr, 2 * idx, 0), mkvar(pp.RH + RH(1, b), arr, 2 * idx + 1, 0)});
+          rho_comb(o, pp, b, q < m ? 0 : 1, q < m ? q : q - m);
         } else if (q < iU) {
-          const int j = q - iRA;
-          if (xg)
-            o.terms({mkvar(pp.RH + RH(1, b), 2, j, 0)});
-          else
-            o.fix(pp.AR + j * 4 + 0 + b, tb_w(0), pp.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0);
+          std::vector<VarTask> terms;
+          head_terms(o, terms, pp, s, q - iRA, b, 2);
+          o.terms(terms);
         } else {
-          const int k = q - iU;
-          o.fix(pp.RH + RH(0, b), tb_u(k, 0), pp.RH + RH(1, b), tb_u(k, 1), 0xFF, 0);
+          emit_U(o, pp, q - iU, b);
         }
       });
-      const ArrTab arrs = arr_tab({{0, xcoms, (uint32_t)(m * Z::COM1)}, {1, theta, (uint32_t)(ky * Z::COM1)}, {2, A, 0, xg}});
+      const ArrTab arrs =
+          arr_tab({{0, v.xcoms, (uint32_t)(m * Z::COM1)}, {1, v.theta, (uint32_t)(ky * Z::COM1)}, {2, v.A, 0, xg}});
       const OutTab outs = out_tab(s1, (uint32_t)(n1 * Z::COM1));
       RC((run_side<C, F1>(c, ".q1", N, sp, arrs, (const S*)pool, pp.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
@@ -2416,7 +2434,7 @@ template <class C> struct Impl {
       sp.tm = TM(8);
       ComOutputs{sp}.add(n, 0, 0, [&](int j, int b, ComOutputs& o) {
         std::vector<VarTask> terms;
-        for (int i = 0; i < m; i++) terms.push_back(mkvar(ps.GC + i * n + j, 0, 2 * i + b, 0));
+        com_terms(terms, ps.GC + j, n, m, 0, b);
         o.fix(0, 0xFF, 0, 0xFF, 0, 2 * (iRA + j) + b);
         o.terms(terms);
       });
@@ -2436,9 +2454,9 @@ template <class C> struct Impl {
       SidePlan sp;
       sp.tm = TM(8);
       ComOutputs{sp}.add(kx, 0, 0, [&](int k, int a, ComOutputs& o) {
-        o.terms({mkvar(pp.RH + RH(a, 0), 0, 2 * k + 0, 0), mkvar(pp.RH + RH(a, 1), 0, 2 * k + 1, 0)});
+        o.terms({mkvar(pp.RH + 2 * a, 0, 2 * k, 0), mkvar(pp.RH + 2 * a + 1, 0, 2 * k + 1, 0)});
       });
-      const ArrTab arrs = arr_tab({{0, pi, (uint32_t)(kx * Z::COM2)}});
+      const ArrTab arrs = arr_tab({{0, v.pi, (uint32_t)(kx * Z::COM2)}});
       const OutTab outs = out_tab(s3, (uint32_t)(kx * Z::COM2));
       RC((run_side<C, F2>(c, ".q3", N, sp, arrs, (const S*)pool, pp.total, (const A2*)c->tabs->tab16_g2.p, outs)));
       RC(scratch(c, "eqrlc.pisum", kx * Z::COM2, &pisum));
@@ -2452,44 +2470,31 @@ template <class C> struct Impl {
       SidePlan sp;
       sp.tm = yg ? 1 : TM(8);  // (MSMEG2's only output has no variable-base term)
       ComOutputs{sp}.add(nb, 0, 0, [&](int q, int b, ComOutputs& o) {
-        std::vector<VarTask> terms;
-        if (!yg && q == iPB) {
-          for (int i = 0; i < m; i++) terms.push_back(mkvar(ps.BC + i, 0, 2 * i + b, 0));  // b_i sum_e C'_e,ib
-          if (ty == GS_MSMEG1) {
-            VarTask v = mkvar(ps.RH + RH(1, b), 1, 0, 0);  // - r_1b t
-            v.neg = 1;
-            terms.push_back(v);
-          }
-          if (ty == GS_QUAD) o.fix(ps.NR + 0 + b, tb_w(0), ps.NR + 2 + b, tb_w(1), 0xFF, 0);
-        } else {
-          o.fix(ps.RH + RH(0, b), tb_w(0), ps.RH + RH(1, b), tb_w(1), 0xFF, 0);
-        }
-        o.terms(terms);
+        if (!yg && q == iPB)
+          emit_PB(o, ps, s, b, 0, 1);  // over sum_e C'_e,i, with r_ab for rho_ab
+        else
+          emit_W1(o, ps, b);
       });
-      const ArrTab arrs = arr_tab({{0, ssum, 0}, {1, target, 0, ty == GS_MSMEG1}});
+      const ArrTab arrs = arr_tab({{0, ssum, 0}, {1, v.target, 0, ty == GS_MSMEG1}});
       const OutTab outs = out_tab(sb, (uint32_t)(nb * Z::COM1));
       RC((run_side<C, F1>(c, ".q4", 1, sp, arrs, (const S*)spool, 0, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
     // ---- Miller.  Per proof: P arrays 0 = s2, 1 = s1; Q arrays 0 ycoms, 3 pi
-    std::vector<PairRef> pr, prb;
-    for (int b = 0; b < 2; b++) {
-      for (int j = 0; j < n; j++) add_pair(pr, 0, 2 * j + b, 0, 0, 2 * j + b);
-      if (!fold_pi)
-        for (int k = 0; k < kx; k++) add_pair(pr, 1, 2 * (iU + k) + b, 1, 3, 2 * k + b);
-    }
     // per batch: P arrays 0 = sb, 1 = ssum, 2 = crs G1 (u, W1); Q arrays 1 B, 2 crs G2 (v, W2), 3 = pisum, 4 target
-    for (int b = 0; b < 2; b++) {
-      if (yg) {
-        if (b == 1)
-          for (int i = 0; i < m; i++) add_pair(prb, 1, 2 * i + 1, 0, 1, i);
-      } else {
-        add_pair(prb, 0, 2 * iPB + b, 0, 2, 4 + b);
-      }
-      for (int l = 0; l < ky; l++) add_pair(prb, 1, 2 * (iTh + l) + b, 1, 2, 2 * l + b);
-      if (fold_pi)
-        for (int k = 0; k < kx; k++) add_pair(prb, 2, 2 * k + b, 1, 3, 2 * k + b);  // (-u_k.a, Pi_k.a), a = b here
-      if (ty == GS_MSMEG2 && b == 1) add_pair(prb, 0, 2 * iW + 1, 1, 4, 0);
-    }
+    std::vector<PairRef> pr, prb;
+    for (int b = 0; b < 2; b++)
+      add_pairs(pr,
+                {{{0, 0}, {0, 0}, n, 0},                           // (P'_e,j, d_e,j)
+                 {{1, iU}, {3, 0}, fold_pi ? 0 : kx, 1}},          // (-U'_e,k, pi_e,k)
+                b, b);
+    for (int b = 0; b < 2; b++)
+      add_pairs(prb,
+                {{{1, 0}, {1, 0, false}, yg ? m : 0, 0},                    // (sum_e C'_e,i, B_i)
+                 {{0, iPB}, {2, 2}, yg ? 0 : 1, 0},                         // (PB, W2)
+                 {{1, iTh}, {2, 0}, ky, 1},                                 // (-sum_e Th'_e,l, v_l)
+                 {{2, 0}, {3, 0}, fold_pi ? kx : 0, 1},                     // (-u_k.a, Pi_k.a), a = b here
+                 {{0, iW}, {4, 0, false}, ty == GS_MSMEG2 ? 1 : 0, 1}},     // (-W1', t)
+                b, b);
     const std::vector<MillerTask> mt = plan_miller_single(c, N, pr), mtb = plan_miller_single(c, 1, prb);
     const int ntask = (int)mt.size(), ntb = (int)mtb.size();
     const size_t nparts = N * ntask + ntb;
@@ -2502,27 +2507,25 @@ template <class C> struct Impl {
       RC(upload(c, "eqrlc.mt", mt, &dmt));
       RC(upload(c, "eqrlc.mtb", mtb, &dmtb));
       const ArrTab parr = arr_tab({{0, s2, (uint32_t)(n * Z::COM1)}, {1, s1, (uint32_t)(n1 * Z::COM1)}});
-      const ArrTab qarr = arr_tab({{0, ycoms, (uint32_t)(n * Z::COM2)}, {3, pi, (uint32_t)(kx * Z::COM2)}});
+      const ArrTab qarr = arr_tab({{0, v.ycoms, (uint32_t)(n * Z::COM2)}, {3, v.pi, (uint32_t)(kx * Z::COM2)}});
       // the batch-level pairs are one wave: they ride along as a second segment of the per-proof launch (a launch of
       // their own would add a serial Miller lane to every call: k_miller.eqrlc.batch in profiles/eq_rlc/rate.json)
       miller_work_hint(c, N, mt, false);
       const LaunchRec per = seg_rec<k_miller<C, false>>(c, "k_miller.eqrlc", N * ntask, 64, N * ntask, ntask, dmt, parr,
                                                         qarr, (GT*)mpart, 1, lines(c));
       const ArrTab parb = arr_tab({{0, sb, 0, nb > 0}, {1, ssum, 0}, {2, c->tabs->crs_g1.p, 0}});
-      const ArrTab qarb = arr_tab({{1, B, 0, yg}, {2, c->tabs->crs_g2.p, 0}, {3, pisum, 0, fold_pi}, {4, target, 0, ty == GS_MSMEG2}});
+      const ArrTab qarb =
+          arr_tab({{1, v.B, 0, yg}, {2, c->tabs->crs_g2.p, 0}, {3, pisum, 0, fold_pi}, {4, v.target, 0, ty == GS_MSMEG2}});
       miller_work_hint(c, 1, mtb, false);
       const LaunchRec bat = seg_rec<k_miller<C, false>>(c, "k_miller.eqrlc.batch", (size_t)ntb, 64, (size_t)ntb, ntb, dmtb,
                                                         parb, qarb, (GT*)mpart + N * ntask, 1, lines(c));
       RC(seg_pair(c, bat, per));  // (the single wave in the first block of the grid)
     }
-    uint8_t* a = (uint8_t*)acc;
-    RC(gt_product(c, nparts, (GT*)mpart, (GT*)tmp, a));
+    RC(gt_product(c, nparts, (GT*)mpart, (GT*)tmp, (uint8_t*)acc));
     if (ty == GS_PPE)
-      RC(launch(c, "k_eq_rlc_tpow", k_eq_rlc_tpow<C>, 1, 64, (const uint8_t*)target, (const S*)spool + ps.RH + 3, (GT*)pt));
-    else
-      RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, (GT*)pt));
-    RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)pt, a + Z::GT));
-    return GS_OK;
+      RC(launch(c, "k_eq_rlc_tpow", k_eq_rlc_tpow<C>, 1, 64, (const uint8_t*)v.target, (const S*)spool + ps.RH + 3,
+                (GT*)pt));
+    return put_acc1(c, ty == GS_PPE ? (const GT*)pt : nullptr, (GT*)pt, acc);
   }
 
   // The batched verifier with fault localisation.  Same front; the products are a K-ary tree whose
@@ -2532,14 +2535,13 @@ template <class C> struct Impl {
   //   rlc.lvl.f / rlc.lvl.t   the levels, one after the other (t only for PPE: it is one everywhere else)
   //   rlc.frontier            u32: counts[0 .. L + 1] (failing nodes per level; [L + 1] = 1, the root's virtual parent),
   //                           then the lists of levels 1 .. L and the virtual parent's list {0}
-  static int verify_rlc_locate(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
-                               const void* target, const void* xcoms, const void* ycoms, const void* pi,
-                               const void* theta, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
+  static int verify_rlc_locate(gs_ctx* c, const VerifyIn& v, const uint64_t* rho, void* acc, uint8_t* ok, uint32_t* info) {
+    const size_t N = v.N;
     void* mpart;
     int ntask;
-    RC(rlc_front(c, ty, N, m, n, A, B, G, target, xcoms, ycoms, pi, theta, rho, &mpart, &ntask));
+    RC(rlc_front(c, v, rho, &mpart, &ntask));
     const int K = c->locate_k ? c->locate_k : 8;  // planned: the arity of gt_product
-    const bool ppe = ty == GS_PPE;
+    const bool ppe = v.sh.ty == GS_PPE;
     std::vector<size_t> cnt{N}, off{0};
     while (cnt.back() > 1) {
       off.push_back(off.back() + cnt.back());
@@ -2562,22 +2564,16 @@ template <class C> struct Impl {
     HIPCHK(c, hipMemsetAsync(info, 0, 2 * sizeof(uint32_t), st));
     // ---- the levels
     RC(launch(c, "k_rlc_leaf", k_rlc_leaf<C>, N, 64, N, ntask, (const GT*)mpart, F));
-    if (ppe) RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, N, 64, N, (const uint8_t*)target, rho, T));
+    if (ppe) RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, N, 64, N, (const uint8_t*)v.target, rho, T));
     for (int l = 1; l <= L; l++) {
       const size_t half = (cnt[l] + 63) / 64 * 64;
       RC(launch(c, "k_rlc_tree", k_rlc_tree<C>, ppe ? half + cnt[l] : cnt[l], 64, cnt[l - 1], (const GT*)(F + off[l - 1]),
                 (const GT*)(ppe ? T + off[l - 1] : nullptr), cnt[l], F + off[l], ppe ? T + off[l] : nullptr, K));
     }
-    uint8_t* a = (uint8_t*)acc;
-    RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)(F + off[L]), a));
-    if (ppe) {
-      RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)(T + off[L]), a + Z::GT));
-    } else {
-      void* one;
-      RC(scratch(c, "rlc.one", sizeof(GT), &one));
-      RC(launch(c, "k_gt_set_one", k_gt_set_one<C>, 1, 64, (GT*)one));
-      RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)one, a + Z::GT));
-    }
+    RC(launch(c, "k_gt_export", k_gt_export<C>, 1, 64, (size_t)1, (const GT*)(F + off[L]), (uint8_t*)acc));
+    void* one = nullptr;
+    if (!ppe) RC(scratch(c, "rlc.one", sizeof(GT), &one));
+    RC(put_acc1(c, ppe ? T + off[L] : nullptr, (GT*)one, acc));
     // ---- the descent: level L is the root under its virtual parent, level 0 the leaves
     for (int l = L; l >= 0; l--) {
       LocateLevel lv;
@@ -2589,11 +2585,10 @@ template <class C> struct Impl {
       lv.fan = l == L ? 1 : K;
       lv.ok = l ? nullptr : ok;
       lv.info = info;
-      const size_t items = l == L ? 1 : cnt[l + 1] * (size_t)K, coop_waves = (items + 20) / 21;
+      const size_t items = l == L ? 1 : cnt[l + 1] * (size_t)K;
       const GT *Fl = F + off[l], *Tl = ppe ? T + off[l] : nullptr;
-      // one lane per node check once the level's launch fills the chip, 3-lane groups (21 per wave) below that
-      if (c->coop_fe == 2 || (c->coop_fe == 1 && coop_waves <= c->simd_slots))
-        RC(launch(c, "k_rlc_locate.coop", k_rlc_locate_coop<C>, coop_waves * 63, 63, lv, Fl, Tl));
+      if (coop_lanes(c, items))  // (the level's own launch: not fillN)
+        RC(launch(c, "k_rlc_locate.coop", k_rlc_locate_coop<C>, (items + 20) / 21 * 63, 63, lv, Fl, Tl));
       else
         RC(launch(c, "k_rlc_locate", k_rlc_locate<C>, items, 64, lv, Fl, Tl));
     }
@@ -2613,22 +2608,16 @@ template <class C> struct Impl {
   // The engine's unit is the statement (N := S): array strides are per statement, p_idx runs over (e, j).  Short
   // (64-bit) and full-size terms go to separate Straus lanes, so the short ones skip their leading windows; outputs
   // over the same bases (the two components of every output above) share a table build (share_tables).
-  static int verify_stmt_rlc(gs_ctx* c, int ty, size_t S, size_t E_, int m, int n, const void* A, const void* B,
-                             const void* G, const void* target, const void* xcoms, const void* ycoms, const void* pi,
-                             const void* theta, const uint64_t* rho, void* acc, uint8_t* ok) {
-    const bool xg = x_is_group(ty), yg = y_is_group(ty);
-    const int kx = xg ? 2 : 1, ky = yg ? 2 : 1, E = (int)E_;
+  // v.N: the statements
+  static int verify_stmt_rlc(gs_ctx* c, const VerifyIn& v, size_t E_, const uint64_t* rho, void* acc, uint8_t* ok) {
+    const Shape& s = v.sh;
+    const int ty = s.ty, m = s.m, n = s.n, kx = s.kx, ky = s.ky, E = (int)E_;
+    const bool xg = s.xg, yg = s.yg;
+    const size_t S = v.N;
     RangeGuard rg_all("gs.verify_stmt_rlc");
-    PoolMap pm;
-    memset(&pm, 0, sizeof pm);
-    int o = 0;
-    pm.RH = o; o += 4 * E;
-    pm.GC = o; o += 4 * m * n;
-    pm.AR = o; o += xg ? 0 : 4 * n;
-    pm.BC = o; o += yg ? 0 : 4 * m;
-    pm.NR = o; o += ty == GS_QUAD ? 4 : 0;
-    pm.total = o;
-    const int nout = o;
+    const PoolMap pm = pool_layout({{&PoolMap::RH, 4 * E}, {&PoolMap::GC, 4 * m * n}, {&PoolMap::AR, xg ? 0 : 4 * n},
+                                    {&PoolMap::BC, yg ? 0 : 4 * m}, {&PoolMap::NR, ty == GS_QUAD ? 4 : 0}});
+    const int nout = pm.total;
     void* pool;
     RC(scratch(c, "srlc.pool", S * pm.total * sizeof(Fr<C>), &pool));
     {
@@ -2639,8 +2628,8 @@ template <class C> struct Impl {
       const int per = narrow ? 1 : nout;
       c->work_hint = S * (uint64_t)E * (uint64_t)(nout - 4 * E + 4);
       RC(launch(c, "k_prep_verify_stmt_rlc", k_prep_verify_stmt_rlc<C>, S * (size_t)per, 64, S, E, m, n, nout, per,
-                (const Fr<C>*)G, xg ? nullptr : (const Fr<C>*)A, yg ? nullptr : (const Fr<C>*)B,
-                ty == GS_QUAD ? (const Fr<C>*)target : nullptr, rho, pm, (Fr<C>*)pool));
+                (const Fr<C>*)v.G, xg ? nullptr : (const Fr<C>*)v.A, yg ? nullptr : (const Fr<C>*)v.B,
+                ty == GS_QUAD ? (const Fr<C>*)v.target : nullptr, rho, pm, (Fr<C>*)pool));
     }
     auto RH = [&](int e, int a, int b) { return pm.RH + 4 * e + 2 * a + b; };
     const int tm = c->endo ? 8 : 1;  // endo = 0: one plain double-and-add lane per term, as everywhere else
@@ -2658,7 +2647,7 @@ template <class C> struct Impl {
           if (xg)
             for (int e = 0; e < E; e++) shortt.push_back(mkvar(RH(e, 1, b), 1, e * n + j, 0));
           else
-            o.fix(pm.AR + j * 4 + 0 + b, tb_w(0), pm.AR + j * 4 + 2 + b, tb_w(1), 0xFF, 0);
+            rho_fix(o, pm.AR + j * 4, b, tb_w(0), tb_w(1));
           for (int i = 0; i < m; i++)
             for (int a = 0; a < 2; a++) full.push_back(mkvar(pm.GC + ((2 * a + b) * m + i) * n + j, 0, 2 * i + a, 0));
         } else if (!yg && q == iPB) {
@@ -2670,7 +2659,7 @@ template <class C> struct Impl {
               v.neg = 1;
               shortt.push_back(v);
             }
-          if (ty == GS_QUAD) o.fix(pm.NR + 0 + b, tb_w(0), pm.NR + 2 + b, tb_w(1), 0xFF, 0);
+          if (ty == GS_QUAD) rho_fix(o, pm.NR, b, tb_w(0), tb_w(1));
         } else {
           const int l = q - iTh;
           for (int e = 0; e < E; e++)
@@ -2679,10 +2668,10 @@ template <class C> struct Impl {
         o.terms(shortt);
         o.terms(full);
       });
-      const ArrTab arrs = arr_tab({{0, xcoms, (uint32_t)(m * Z::COM1)},
-                                   {1, A, (uint32_t)((size_t)E * n * Z::G1), xg},
-                                   {2, target, (uint32_t)((size_t)E * Z::G1), ty == GS_MSMEG1},
-                                   {3, theta, (uint32_t)((size_t)E * ky * Z::COM1)}});
+      const ArrTab arrs = arr_tab({{0, v.xcoms, (uint32_t)(m * Z::COM1)},
+                                   {1, v.A, (uint32_t)((size_t)E * n * Z::G1), xg},
+                                   {2, v.target, (uint32_t)((size_t)E * Z::G1), ty == GS_MSMEG1},
+                                   {3, v.theta, (uint32_t)((size_t)E * ky * Z::COM1)}});
       const OutTab outs = out_tab(s1, (uint32_t)(n1 * Z::COM1));
       RC((run_side<C, F1>(c, ".s1", S, sp, arrs, (const Fr<C>*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs)));
     }
@@ -2706,29 +2695,32 @@ template <class C> struct Impl {
         }
         o.terms(terms);
       });
-      const ArrTab arrs = arr_tab({{0, B, (uint32_t)((size_t)E * m * Z::G2), yg},
-                                   {1, pi, (uint32_t)((size_t)E * kx * Z::COM2)},
-                                   {2, target, (uint32_t)((size_t)E * Z::G2), ty == GS_MSMEG2}});
+      const ArrTab arrs = arr_tab({{0, v.B, (uint32_t)((size_t)E * m * Z::G2), yg},
+                                   {1, v.pi, (uint32_t)((size_t)E * kx * Z::COM2)},
+                                   {2, v.target, (uint32_t)((size_t)E * Z::G2), ty == GS_MSMEG2}});
       const OutTab outs = out_tab(s2, (uint32_t)(n2 * Z::COM2));
       RC((run_side<C, F2>(c, ".s2", S, sp, arrs, (const Fr<C>*)pool, pm.total, (const A2*)c->tabs->tab16_g2.p, outs)));
     }
     // ---- Miller.  P arrays: 0 = S1, 1 = xcoms, 2 = crs G1 (u, W1).  Q arrays: 0 ycoms, 1 = S2, 2 = crs G2 (v, W2)
     std::vector<PairRef> pr;
-    for (int b = 0; b < 2; b++) {
-      for (int j = 0; j < n; j++) add_pair(pr, 0, 2 * j + b, 0, 0, 2 * j + b);            // (P_j.b, d_j.b)
-      if (!yg) add_pair(pr, 0, 2 * iPB + b, 0, 2, 4 + b);                                 // (PB.b, W2.b)
-      for (int l = 0; l < ky; l++) add_pair(pr, 0, 2 * (iTh + l) + b, 1, 2, 2 * l + b);   // (-Th_l.b, v_l.b)
-    }
-    for (int a = 0; a < 2; a++) {
-      if (yg)
-        for (int i = 0; i < m; i++) add_pair(pr, 1, 2 * i + a, 0, 1, 2 * i + a);          // (c_i.a, Q_i.a)
-      for (int k = 0; k < kx; k++) add_pair(pr, 2, 2 * k + a, 1, 1, 2 * (iPi + k) + a);   // (-u_k.a, Pi_k.a)
-      if (ty == GS_MSMEG2) add_pair(pr, 2, 4 + a, 1, 1, 2 * iT + a);                      // (-W1.a, T.a)
-    }
+    for (int b = 0; b < 2; b++)
+      add_pairs(pr,
+                {{{0, 0}, {0, 0}, n, 0},                   // (P_j.b, d_j.b)
+                 {{0, iPB}, {2, 2}, yg ? 0 : 1, 0},        // (PB.b, W2.b)
+                 {{0, iTh}, {2, 0}, ky, 1}},               // (-Th_l.b, v_l.b)
+                b, b);
+    for (int a = 0; a < 2; a++)
+      add_pairs(pr,
+                {{{1, 0}, {1, 0}, yg ? m : 0, 0},                      // (c_i.a, Q_i.a)
+                 {{2, 0}, {1, iPi}, kx, 1},                            // (-u_k.a, Pi_k.a)
+                 {{2, 2}, {1, iT}, ty == GS_MSMEG2 ? 1 : 0, 1}},       // (-W1.a, T.a)
+                a, a);
     const std::vector<MillerTask> mt = plan_miller_single(c, S, pr);
     const int ntask = (int)mt.size();
-    const ArrTab parr = arr_tab({{0, s1, (uint32_t)(n1 * Z::COM1)}, {1, xcoms, (uint32_t)(m * Z::COM1)}, {2, c->tabs->crs_g1.p, 0}});
-    const ArrTab qarr = arr_tab({{0, ycoms, (uint32_t)(n * Z::COM2)}, {1, s2, (uint32_t)(n2 * Z::COM2)}, {2, c->tabs->crs_g2.p, 0}});
+    const ArrTab parr =
+        arr_tab({{0, s1, (uint32_t)(n1 * Z::COM1)}, {1, v.xcoms, (uint32_t)(m * Z::COM1)}, {2, c->tabs->crs_g1.p, 0}});
+    const ArrTab qarr =
+        arr_tab({{0, v.ycoms, (uint32_t)(n * Z::COM2)}, {1, s2, (uint32_t)(n2 * Z::COM2)}, {2, c->tabs->crs_g2.p, 0}});
     void* mpart;
     RC(miller_single(c, "srlc", S, mt, parr, qarr, &mpart));
     // ---- PPE: T_s = prod_e t_e^rho_e,11 (segmented K-ary product of k_rlc_tpow's S E powers)
@@ -2738,7 +2730,7 @@ template <class C> struct Impl {
       void *t0, *t1;
       RC(scratch(c, "srlc.t0", S * (size_t)E * sizeof(GT), &t0));
       RC(scratch(c, "srlc.t1", S * (((size_t)E + K - 1) / K) * sizeof(GT), &t1));
-      RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, S * (size_t)E, 64, S * (size_t)E, (const uint8_t*)target, rho, (GT*)t0));
+      RC(launch(c, "k_rlc_tpow", k_rlc_tpow<C>, S * (size_t)E, 64, S * (size_t)E, (const uint8_t*)v.target, rho, (GT*)t0));
       GT *in = (GT*)t0, *out = (GT*)t1;
       for (size_t len = (size_t)E; len > 1;) {
         size_t lo = (len + K - 1) / K;
@@ -2748,10 +2740,9 @@ template <class C> struct Impl {
       }
       tprod = in;
     }
-    // ---- one final exponentiation per statement: one lane each once that fills the chip, 3-lane groups below that
-    size_t coop_waves = (S + 20) / 21;
-    if (c->coop_fe == 2 || (c->coop_fe == 1 && (fillN(c, S) + 20) / 21 <= c->simd_slots))
-      RC(launch_seg<k_stmt_final_coop<C>>(c, "k_stmt_final.coop", coop_waves * 63, 63, S, ntask, (const GT*)mpart, tprod,
+    // ---- one final exponentiation per statement
+    if (coop_lanes(c, fillN(c, S)))
+      RC(launch_seg<k_stmt_final_coop<C>>(c, "k_stmt_final.coop", (S + 20) / 21 * 63, 63, S, ntask, (const GT*)mpart, tprod,
                 (uint8_t*)acc, ok));
     else
       RC(launch_seg<k_stmt_final<C>>(c, "k_stmt_final", S, 64, S, ntask, (const GT*)mpart, tprod, (uint8_t*)acc, ok));
@@ -2903,10 +2894,7 @@ static int left_mul_impl(gs_ctx* c, int rows, int k, const void* lhs, const void
   RC(st.in(col, (size_t)k * com, &dc));
   RC(st.out(out, (size_t)rows * com, &dout));
   // pool = canonical lhs via k_prep_verify (m*n scalars)
-  PoolMap pm;
-  memset(&pm, 0, sizeof pm);
-  pm.GC = 0;
-  pm.total = rows * k;
+  const PoolMap pm = pool_layout({{&PoolMap::GC, rows * k}});
   void* pool;
   RC(scratch(c, "lm.pool", (size_t)pm.total * sizeof(S), &pool));
   RC(launch_seg<k_prep_verify<C>>(c, "k_prep_verify", 1, 64, (size_t)1, rows, k, (const S*)dl, (const S*)nullptr,
@@ -3583,9 +3571,7 @@ static const int* verify_order(int ty) {
   return ty == GS_PPE || ty == GS_MSMEG2 ? order_g : order_s;
 }
 static int verify_run(gs_ctx* c, const BatchArgs& a) {
-  const void* const* p = a.p;
-  return DISPATCH(c, verify(c, a.ty, a.N, a.m, a.n, p[VI_A], p[VI_B], p[VI_G], p[VI_TG], p[VI_XC], p[VI_YC], p[VI_PI],
-                            p[VI_TH], (uint8_t*)a.out(VO_OK), a.shared));
+  return DISPATCH(c, verify(c, VerifyIn(a.ty, a.N, a.m, a.n, a.p), (uint8_t*)a.out(VO_OK), a.shared));
 }
 static const Op kVerify = {kVerifyArrs, sizeof kVerifyArrs / sizeof *kVerifyArrs, verify_order, 8, verify_run};
 static BatchArgs from_part(const gs_verify_part& p) {
@@ -4218,22 +4204,18 @@ static int rlc_check(gs_ctx* c, const RlcCall& k, bool host, RlcArr* a, int* na)
 }
 // the kernels of a checked call (device pointers)
 static int rlc_run(gs_ctx* c, const RlcCall& k) {
-  const void* const* p = k.p;
-  const uint64_t* rho = (const uint64_t*)p[RLC_RHO];
+  const VerifyIn v(k.ty, k.v == RLC_STMT ? k.S : k.N, k.m, k.n, k.p);  // (k.p[0 .. 7] are the slots VI_A .. VI_TH)
+  const uint64_t* rho = (const uint64_t*)k.p[RLC_RHO];
   uint8_t* ok = (uint8_t*)k.out(RLC_OK);
   switch (k.v) {
     case RLC_PLAIN:
-      return DISPATCH(c, verify_rlc(c, k.ty, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], rho,
-                                    k.out(RLC_ACC)));
+      return DISPATCH(c, verify_rlc(c, v, rho, k.out(RLC_ACC)));
     case RLC_LOCATE:
-      return DISPATCH(c, verify_rlc_locate(c, k.ty, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], rho,
-                                           k.out(RLC_ACC), ok, (uint32_t*)k.out(RLC_INFO)));
+      return DISPATCH(c, verify_rlc_locate(c, v, rho, k.out(RLC_ACC), ok, (uint32_t*)k.out(RLC_INFO)));
     case RLC_STMT:
-      return DISPATCH(c, verify_stmt_rlc(c, k.ty, k.S, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7],
-                                         rho, k.out(RLC_ACC), ok));
+      return DISPATCH(c, verify_stmt_rlc(c, v, k.N, rho, k.out(RLC_ACC), ok));
     case RLC_EQ:
-      return DISPATCH(c, verify_eq_rlc(c, k.ty, k.N, k.m, k.n, p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], rho,
-                                       k.out(RLC_ACC)));
+      return DISPATCH(c, verify_eq_rlc(c, v, rho, k.out(RLC_ACC)));
   }
   return GS_ERR_ARG;
 }
