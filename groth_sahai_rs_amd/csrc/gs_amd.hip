@@ -2870,8 +2870,11 @@ static void clear_extraction_key(gs_ctx* c) {
   c->have_xkey = false;
   if (!c->xkey.p) return;
   hipSetDevice(c->device);
-  hipStreamSynchronize(c->stream);  // extractions already enqueued still read the streams
-  hipMemset(c->xkey.p, 0, c->xkey.cap);
+  drain_ctx(c);  // extractions already enqueued still read the streams
+  // on the context's stream, and finished before this returns: a null-stream memset is ordered against nothing on a
+  // non-blocking caller stream, where the next key's k_extract_key would race it
+  hipMemsetAsync(c->xkey.p, 0, c->xkey.cap, c->stream);
+  hipStreamSynchronize(c->stream);
 }
 
 static int check_ctx(gs_ctx* c, bool need_crs) {
@@ -3157,6 +3160,12 @@ void gs_ctx_destroy(gs_ctx* c) {
 
 int gs_set_stream(gs_ctx* c, void* s) {
   if (!c) return GS_ERR_ARG;
+  if ((hipStream_t)s != c->stream) {
+    // the named scratch buffers, the side streams and their events are shared by consecutive calls and ordered only
+    // through the context's stream: work in flight on the old one finishes before anything goes to the new one
+    RC(check_ctx(c, false));
+    drain_ctx(c);
+  }
   c->stream = (hipStream_t)s;
   return GS_OK;
 }
@@ -3224,6 +3233,10 @@ int gs_set_option(gs_ctx* c, const char* key, int value) {
 int gs_sync(gs_ctx* c) {
   RC(check_ctx(c, false));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  // every call joins its side streams into the context's stream before it returns; a call that failed half way may
+  // not have, and gs_sync promises the whole context
+  for (hipStream_t st : c->side)
+    if (st) HIPCHK(c, hipStreamSynchronize(st));
   return GS_OK;
 }
 const char* gs_last_error(gs_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -3313,6 +3326,7 @@ int gs_host_free(gs_ctx* c, void* ptr) {
 int gs_set_crs(gs_ctx* c, const void* crs) {
   RC(check_ctx(c, false));
   if (!crs) return GS_ERR_ARG;
+  drain_ctx(c);  // kernels in flight read the tables this call may free (their last reference can be this context's)
   clear_extraction_key(c);  // a key belongs to the CRS it was checked against
   return DISPATCH(c, set_crs(c, crs));
 }

@@ -74,7 +74,19 @@ enum { GS_OK = 0, GS_ERR_SHAPE = 1, GS_ERR_DEVICE = 2, GS_ERR_ARG = 3, GS_ERR_NO
 int gs_ctx_create(int curve_id, int device_ordinal, gs_ctx** out);
 void gs_ctx_destroy(gs_ctx* ctx);
 /* Several GPUs: one context per device ordinal, sharded by the caller, or gs_ctx_create_multi below. */
-int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default stream */
+/* The context's stream (hipStream_t; NULL = the default stream), blocking or not.  ORDERING: a _dev call only enqueues.
+ * Everything it enqueues -- kernels, memsets, copies, and the work it forks to the context's own non-blocking side
+ * streams, which wait for the stream at the fork and are joined back into it before the call returns -- is ordered
+ * after the work already on the stream and before whatever the caller enqueues there next: inputs written on the
+ * stream before the call are seen, outputs may be read on the stream after it, and nothing rests on legacy
+ * null-stream ordering.  A host-pointer call returns when its outputs are in the caller's memory; work the caller has
+ * in flight on the stream is waited for first.  One context serves one host thread at a time; contexts of different
+ * threads are independent (they share the CRS tables and the page-lock registry, both behind locks).
+ * Changing the handle needs no caller-side sync: when it differs from the current one, gs_set_stream first drains the
+ * context (its stream, side streams and copy queues) -- consecutive calls share named scratch buffers and are ordered
+ * through the stream alone, so work in flight on the old stream must not meet the next call's on the new one.
+ * Setting the same handle again costs nothing. */
+int gs_set_stream(gs_ctx* ctx, void* hip_stream);
 /* Planner overrides (results never change, only which kernel shapes run; tests force every shape through them):
  *   "miller_twin"  -1 planned | 0 one accumulator per Miller lane | 1 two (lines of Q shared by both G1 partners)
  *                   | 2 the same triples on a PAIR of lanes, one accumulator each, lines exchanged through LDS | 3 the
@@ -128,7 +140,11 @@ int gs_set_stream(gs_ctx* ctx, void* hip_stream); /* hipStream_t; NULL = default
  * cached or not), GS_PIPE_TRACE=1 (time line of a host-pointer call's staging, uploads and arrivals);
  * GS_PIPE_NO_DIRECT=1 stages registered arrays like pageable ones. */
 int gs_set_option(gs_ctx* ctx, const char* key, int value);
-int gs_sync(gs_ctx* ctx);                         /* hipStreamSynchronize on the context's stream */
+/* hipStreamSynchronize on the context's stream, then on its side streams.  Every call joins what it forked to the
+ * side streams back into the context's stream before it returns, so the first wait already covers them; the second
+ * makes that hold after a call that failed half way.  After gs_sync the outputs of every _dev call made so far may be
+ * read from any stream or copied with a blocking hipMemcpy. */
+int gs_sync(gs_ctx* ctx);
 /* Page-locked caller memory.  The host-pointer entry points below (gs_prove_batch, gs_verify_batch, the mixed and the
  * Statement calls, gs_multi_*) stage pageable arrays through a pinned buffer of their own (one memcpy per array and
  * direction on worker threads).  An array that lies inside a range registered HERE is moved by DMA straight from / to
@@ -171,7 +187,14 @@ int gs_sizes(int curve_id, size_t out[6]);
  *   - large arities only: the shared per-base window tables, N x 2 m bases x 128 entries (affine + Jacobian staging:
  *     36 KB per base in G1; planned only while that stays below 8 GB);
  *   - mixed calls: the above once per PART (the parts' scratch is live at the same time).
- * A pool of W worker contexts on one GPU therefore costs 1.8 GB + W x (the above for the workers' batch size). */
+ * A pool of W worker contexts on one GPU therefore costs 1.8 GB + W x (the above for the workers' batch size).
+ * ON A LIVE CONTEXT the call may be repeated with another CRS.  ORDERING: it first drains the context (stream, side
+ * streams, copy queues), so calls in flight finish under the CRS they were made with before this context's reference
+ * on the old tables goes (the tables are freed when no other context holds them); it returns when the new tables are
+ * built, and synchronises the context's stream on the way.  The extraction key is forgotten and its digit streams
+ * zeroed (a key belongs to the CRS it was checked against: gs_extract_* give GS_ERR_ARG until gs_set_extraction_key is
+ * called again, also when the same CRS comes back).  The tables of gs_dlog_prepare are not tied to the CRS and stay.
+ * Other contexts that hold the old CRS are not touched. */
 int gs_set_crs(gs_ctx* ctx, const void* crs_host);
 
 /* CRS of the reference's shape (src/generator.rs:81-118, binding key :48-60) from caller-drawn values:
@@ -405,7 +428,9 @@ int gs_verify_mixed(gs_ctx*, int nparts, const gs_verify_part* parts);
  * one final exponentiation for the whole batch.  *ok_all = 1 iff the combined
  * check passes; acc (may be NULL for the host entry) receives the accumulator PAIR
  * (2 GT): acc[0] = prod Miller(e,cell)^rho (un-exponentiated), acc[1] = prod t_e^rho
- * (1 for the non-PPE types).  Ranks exchange their pairs (all-gather) and
+ * (1 for the non-PPE types).  acc[0] is defined up to factors the final exponentiation removes: its BYTES are a
+ * function of the inputs and of "line_tables" (tabulated and stepped lines differ by elements of a proper subfield),
+ * never of what the context did before; acc[1] and the verdict follow no option.  Ranks exchange their pairs (all-gather) and
  * gs_gt_finalize(count, pairs) multiplies them in the given order and checks
  * FE(prod acc[0]) == prod acc[1]: the verdict for the union of the batches. */
 int gs_verify_batch_rlc_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
