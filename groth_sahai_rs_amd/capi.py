@@ -42,7 +42,14 @@ SYMBOLS = [
     "gs_set_extraction_key", "gs_extract_g1_dev", "gs_extract_g2_dev", "gs_extract_g1", "gs_extract_g2",
     "gs_dlog_prepare", "gs_dlog_g1_dev", "gs_dlog_g2_dev", "gs_dlog_g1", "gs_dlog_g2",
     "gs_extract_scalar_b1_dev", "gs_extract_scalar_b2_dev", "gs_extract_scalar_b1", "gs_extract_scalar_b2",
+    "gs_eval_batch_dev", "gs_eval_batch", "gs_eval_statement_dev", "gs_eval_statement",
+    "gs_check_witness_batch_dev", "gs_check_witness_batch", "gs_check_witness_statement_dev",
+    "gs_check_witness_statement",
 ]
+# (gs_ctx*, int equ_type, size_t N, int m, int n, X, Y, A, B, Gamma, ...): gs_eval_* end in target_out, gs_check_witness_*
+# in target, ok
+_EVAL_ARGTYPES = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
+_CHECK_ARGTYPES = _EVAL_ARGTYPES + [ctypes.c_void_p]
 # (size_t count, const void* in, unsigned bits, void* out_fr, void* found_u8) behind the context
 _DLOG_ARGTYPES = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
 GS_MIXED_MAX = 8
@@ -98,6 +105,10 @@ def load_library():
         for n in SYMBOLS:
             if n.startswith(("gs_dlog_g", "gs_extract_scalar_")):
                 getattr(_LIB, n).argtypes = _DLOG_ARGTYPES
+            elif n.startswith(("gs_eval_", "gs_check_witness_")) and hasattr(_LIB, n):
+                # (hasattr: GS_AMD_LIB may name an older build for an A/B run of the entries it does have; calling an
+                # entry it lacks still fails loudly, with ctypes' AttributeError)
+                getattr(_LIB, n).argtypes = _EVAL_ARGTYPES if n.startswith("gs_eval_") else _CHECK_ARGTYPES
     return _LIB
 
 
@@ -450,6 +461,59 @@ class Engine:
         self._chk(self.lib.gs_verify_statement(self.ctx, ty, ctypes.c_size_t(E), m, n, _p(A), _p(B), _p(Gamma),
                                                _p(target), _p(xcoms), _p(ycoms), _p(pi), _p(theta), _p(ok)))
         return ok
+
+    # -- evaluation: an equation's value at a witness, and whether a witness satisfies it -------------------------
+    def _eval(self, fn, ty, N, m, n, X, Y, A, B, Gamma, target=None, out=None):
+        """gs_eval_* / gs_check_witness_*, host and _dev forms: byte lengths before the ABI is crossed, the output, the
+        call.  A `_statement` entry takes ONE copy of X[m], Y[n].  out: target_out (gs_eval_*) or ok (gs_check_witness_*);
+        a host form's missing output is allocated here, a _dev form's is refused.  Returns the output."""
+        dev, shared, check = fn.endswith("_dev"), "_statement" in fn, fn.startswith("gs_check_witness")
+        names = ("X", "Y", "A", "B", "Gamma") + (("target",) if check else ())
+        arrays = (X, Y, A, B, Gamma) + ((target,) if check else ())
+        if any(a is None for a in arrays):
+            raise GsError(3, "%s: %s is required" % (fn, names[[a is None for a in arrays].index(True)]))
+        if not dev:
+            arrays = tuple(_u8(a) for a in arrays)
+        want = self._check(fn, ty, N, m, n, shared, **dict(zip(names, arrays)))
+        key = "ok" if check else "target_out"
+        if out is None:
+            if dev:
+                raise GsError(3, "%s: %s is required" % (fn, key))
+            out = self._out(want["ok" if check else "target"])
+        self._check(fn, ty, N, m, n, shared, **{key: out})
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, N, m, n, *[_p(a) for a in arrays], _p(out)))
+        return out
+
+    def eval_batch(self, ty, N, m, n, X, Y, A, B, Gamma, target_out=None):
+        """The targets of N equations at their witnesses (gs_eval_batch, host arrays): GT / G1 / G2 / Fr per type, in
+        the form verify_batch takes them.  Returns target_out (N x target bytes)."""
+        return self._eval("gs_eval_batch", ty, N, m, n, X, Y, A, B, Gamma, out=target_out).reshape(N, self.shape(ty)["st"])
+
+    def eval_statement(self, ty, E, m, n, X, Y, A, B, Gamma, target_out=None):
+        """The targets of a Statement's E equations over ONE copy of the variables X[m], Y[n] (gs_eval_statement)."""
+        return self._eval("gs_eval_statement", ty, E, m, n, X, Y, A, B, Gamma, out=target_out).reshape(E, self.shape(ty)["st"])
+
+    def check_witness_batch(self, ty, N, m, n, X, Y, A, B, Gamma, target, ok=None):
+        """ok[e] = 1 iff the witness of equation e satisfies it: its value equals target[e] as an element
+        (gs_check_witness_batch, host arrays).  A target with non-canonical limbs never matches."""
+        return self._eval("gs_check_witness_batch", ty, N, m, n, X, Y, A, B, Gamma, target, ok)
+
+    def check_witness_statement(self, ty, E, m, n, X, Y, A, B, Gamma, target, ok=None):
+        """The same for a Statement's E equations over ONE copy of X[m], Y[n] (gs_check_witness_statement)."""
+        return self._eval("gs_check_witness_statement", ty, E, m, n, X, Y, A, B, Gamma, target, ok)
+
+    def eval_batch_dev(self, ty, N, m, n, X, Y, A, B, Gamma, target_out):
+        """Device form (torch tensors): only enqueues on the context's stream."""
+        self._eval("gs_eval_batch_dev", ty, N, m, n, X, Y, A, B, Gamma, out=target_out)
+
+    def eval_statement_dev(self, ty, E, m, n, X, Y, A, B, Gamma, target_out):
+        self._eval("gs_eval_statement_dev", ty, E, m, n, X, Y, A, B, Gamma, out=target_out)
+
+    def check_witness_batch_dev(self, ty, N, m, n, X, Y, A, B, Gamma, target, ok):
+        self._eval("gs_check_witness_batch_dev", ty, N, m, n, X, Y, A, B, Gamma, target, ok)
+
+    def check_witness_statement_dev(self, ty, E, m, n, X, Y, A, B, Gamma, target, ok):
+        self._eval("gs_check_witness_statement_dev", ty, E, m, n, X, Y, A, B, Gamma, target, ok)
 
     def _rlc(self, fn, ty, S, N, m, n, arrays, rho, **outs):
         """The batched (RLC) verifiers, host and _dev forms: byte lengths, missing outputs, the call.  arrays: A ..

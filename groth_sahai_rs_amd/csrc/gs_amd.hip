@@ -563,6 +563,7 @@ static inline int out_ready(gs_ctx* c, unsigned mask) { return c->pipe ? c->pipe
 enum { PI_X = 0, PI_Y, PI_A, PI_B, PI_G, PI_R, PI_S, PI_T, PO_XC, PO_YC, PO_PI, PO_TH };           // prove
 enum { VI_A = 0, VI_B, VI_G, VI_TG, VI_XC, VI_YC, VI_PI, VI_TH, VO_OK };                            // verify
 enum { RI_A = 0, RI_B, RI_G, RI_R, RI_S, RI_T, RI_XC, RI_YC, RI_PI, RI_TH, RO_XC, RO_YC, RO_PI, RO_TH };  // rerandomize
+enum { EI_X = 0, EI_Y, EI_A, EI_B, EI_G, EI_TG, EO_T, EO_OK };                                      // evaluate / check witness
 #define BIT(i) (1u << (i))
 
 // the batch size the lane-shape planners should fill the chip for: the part's own, or (mixed calls, whose parts'
@@ -1027,6 +1028,7 @@ struct SidePlan {
   int ncom = 0;  // the first `ncom` reductions (the commitments) only sum fixed-base partial slots
   int tab_bases = 0;  // > 0: every variable-base term is over array 0, which holds this many bases per equation, and
                       // the side runs on shared per-base window tables (k_tab_build + k_var_tab) instead of Straus lanes
+  bool points = false;  // the outputs are single points, not Com-shaped pairs: the reductions run k_red_pt
 };
 
 static FixTask mkfix(int s0, int t0, int s1, int t1, int a_arr, int a_idx, int slot, int a_neg = 0) {
@@ -1472,6 +1474,7 @@ struct RedLaunch {
   size_t nred = 0;
   int nslots = 0;
   OutTab outs;
+  bool points = false;  // one point per output (k_red_pt)
 };
 constexpr uint32_t RED_FOLD_K = 8, RED_RUN_MAX = 16;
 template <class C, class F> static int run_red(gs_ctx* c, size_t N, const RedLaunch& r) {
@@ -1518,6 +1521,8 @@ template <class C, class F> static int run_red(gs_ctx* c, size_t N, const RedLau
   while (K < RED_K && K < (int)r.nred && (fillN(c, N) * ((r.nred + 2 * K - 1) / (2 * K)) + 63) / 64 >= c->simd_slots) K *= 2;
   if (c->red_k > 0) K = std::min(c->red_k, RED_K);
   size_t lanes = N * ((r.nred + K - 1) / K);
+  if (r.points)
+    return launch_seg<k_red_pt<C, F>>(c, r.name.c_str(), lanes, 64, lanes, (int)r.nred, dred, part, nslots, r.outs, K);
   return launch_seg<k_red<C, F>>(c, r.name.c_str(), lanes, 64, lanes, (int)r.nred, dred, part, nslots, r.outs, K);
 }
 template <class C, class F>
@@ -1664,6 +1669,7 @@ static int run_side(gs_ctx* c, const char* tag, size_t N, SidePlan& sp, const Ar
   r.nred = r.hred.size();
   r.nslots = sp.nslots;
   r.outs = outs;
+  r.points = sp.points;
   RC((run_red<C, F>(c, N, r)));
   if (pipe_masks) RC(out_ready(c, pipe_masks[2] | pipe_masks[3]));
   return GS_OK;
@@ -2033,15 +2039,16 @@ template <class C> struct Impl {
   static const Line<C>* lines(const gs_ctx* c) { return (const Line<C>*)(c->line_tables ? c->tabs->line_tab.p : nullptr); }
   // Miller tail of the two RLC verifiers: the single-accumulator task list `mt` (plan_miller_single) goes up as `tag`.mt
   // and runs as k_miller.`tag` into the scratch `tag`.mpart (mt.size() partials per equation).
+  // (ostride 2 leaves the partials in the layout k_cell_fold reads: slot 0 of a pair)
   static int miller_single(gs_ctx* c, const std::string& tag, size_t N, const std::vector<MillerTask>& mt,
-                           const ArrTab& parr, const ArrTab& qarr, void** mpart) {
+                           const ArrTab& parr, const ArrTab& qarr, void** mpart, int ostride = 1) {
     const MillerTask* dmt;
     RC(upload(c, (tag + ".mt").c_str(), mt, &dmt));
     const int ntask = (int)mt.size();
-    RC(scratch(c, (tag + ".mpart").c_str(), N * ntask * sizeof(GT), mpart));
+    RC(scratch(c, (tag + ".mpart").c_str(), N * ntask * ostride * sizeof(GT), mpart));
     miller_work_hint(c, N, mt, false);
     return launch_seg<k_miller<C, false>>(c, ("k_miller." + tag).c_str(), N * ntask, 64, N * ntask, ntask, dmt, parr, qarr,
-              (GT*)*mpart, 1, lines(c));
+              (GT*)*mpart, ostride, lines(c));
   }
 
   // Q arrays of the exact verifier and of rlc_front: 0 ycoms, 1 B, 2 crs G2 consts, 3 pi, 4 target (MSMEG2)
@@ -2214,6 +2221,149 @@ template <class C> struct Impl {
       RC(launch_seg<k_final<C>>(c, "k_final", N * 4, 64, N, ntask, cm, (const GT*)mpart, target, (uint8_t*)cellok));
     RC(launch_seg<k_and4>(c, "k_and4", N, 64, N, (const uint8_t*)cellok, ok));
     return GS_OK;
+  }
+
+  // ------------------------------------------------------------- evaluate --
+  // The left-hand side of an equation at a witness (statement.rs:17-21), written to `out` -- or, with out null, compared
+  // with `target` into ok[N] (gs_check_witness_*).  No CRS element is read.
+  //   PPE      W_j = A_j + sum_i Gamma_ij X_i: n outputs over the SAME m bases (share_tables; the shared window tables at
+  //            large arity), A_j the affine addend of a table-less k_fix lane; then prod_j e(W_j, Y_j) prod_i e(X_i, B_i):
+  //            m + n stepped pairs, one accumulator and one final exponentiation per equation
+  //   MSMEG1/2 ONE output over m + n variable-base terms, the Gamma term folded into their scalars by k_prep_eval
+  //   QuadEqu  k_prep_eval alone
+  // shared: a Statement -- ONE copy of X, Y (stride 0) for all N equations.
+  // One MSME output.  G1: array 0 = X (scalars c_i at BC), 1 = A (y_j at YC); G2: array 0 = Y (d_j at AC), 1 = B (x_i at XC)
+  template <class F>
+  static int eval_msme(gs_ctx* c, const Shape& sh, size_t N, const PoolMap& pm, const void* pool, const void* V,
+                       const void* K, const void* target, void* out, uint8_t* ok, bool shared) {
+    constexpr bool g2 = std::is_same<F, F2>::value;
+    const uint32_t zp = (uint32_t)(g2 ? Z::G2 : Z::G1);
+    const int nv = g2 ? sh.n : sh.m, nc = g2 ? sh.m : sh.n, sv = g2 ? pm.AC : pm.BC, sc = g2 ? pm.XC : pm.YC;
+    SidePlan sp;
+    sp.points = true;
+    sp.tm = pick_tm(c, fillN(c, N), nv + nc, 1, g2, 1);
+    std::vector<VarTask> terms;
+    for (int i = 0; i < nv; i++) terms.push_back(mkvar(sv + i, 0, i, 0));
+    for (int j = 0; j < nc; j++) terms.push_back(mkvar(sc + j, 1, j, 0));
+    int slot = 0;
+    add_var_terms(sp, terms, slot);
+    sp.red.push_back(mkred(0, slot, 0, 0, 0, 0));
+    sp.nslots = slot;
+    void* val = out;
+    if (!out) RC(scratch(c, "eval.val", N * zp, &val));
+    const ArrTab arrs = arr_tab({{0, V, shared ? 0u : (uint32_t)nv * zp}, {1, K, (uint32_t)nc * zp}});
+    const OutTab outs = out_tab(val, zp);
+    RangeGuard rg(g2 ? "gs.eval.g2" : "gs.eval.g1");
+    const unsigned masks[4] = {0u, BIT(g2 ? EI_Y : EI_X) | BIT(g2 ? EI_B : EI_A), 0u, out ? BIT(EO_T) : 0u};
+    const void* tab = g2 ? c->tabs->tab16_g2.p : c->tabs->tab16_g1.p;  // (no fixed-base lane: never read)
+    RC((run_side<C, F>(c, g2 ? ".ev2" : ".ev1", N, sp, arrs, (const S*)pool, pm.total, (const Aff<F>*)tab, outs, nullptr,
+                       nullptr, nullptr, masks)));
+    if (out) return GS_OK;
+    RC(need(c, BIT(EI_TG)));
+    return launch_seg<k_eval_cmp>(c, "k_eval_cmp", N, 64, N, (int)(zp / 4), (const uint32_t*)val, (const uint32_t*)target, ok);
+  }
+  static int eval(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A, const void* B,
+                  const void* G, const void* target, void* out, uint8_t* ok, bool shared) {
+    const Shape sh(ty, m, n);
+    const bool wide = wide_prep(m, n), check = out == nullptr;
+    const int sv = shared ? 1 : 0;
+    RangeGuard rg_all("gs.eval");
+    const PoolMap pm = ty == GS_PPE      ? pool_layout({{&PoolMap::GC, m * n}})
+                       : ty == GS_MSMEG1 ? pool_layout({{&PoolMap::YC, n}, {&PoolMap::BC, m}})
+                       : ty == GS_MSMEG2 ? pool_layout({{&PoolMap::XC, m}, {&PoolMap::AC, n}})
+                                         : pool_layout({{&PoolMap::BC, m}});
+    void* pool;
+    RC(scratch(c, "eval.pool", N * pm.total * sizeof(S), &pool));
+    const S *xs = sh.xg ? nullptr : (const S*)X, *ys = sh.yg ? nullptr : (const S*)Y;
+    const S *as = sh.xg ? nullptr : (const S*)A, *bs = sh.yg ? nullptr : (const S*)B;
+    // (host-pointer calls: the scalars first; group-valued arrays are not read before their side)
+    RC(need(c, BIT(EI_G) | (sh.xg ? 0u : BIT(EI_X) | BIT(EI_A)) | (sh.yg ? 0u : BIT(EI_Y) | BIT(EI_B)) |
+                   (ty == GS_QUAD && check ? BIT(EI_TG) : 0u)));
+    if (ty == GS_PPE) {
+      const S* g;
+      RC(prep_gamma(c, N, m, n, G, pm, pool, &g));
+      if (g)
+        RC(launch_seg<k_prep_eval<C>>(c, "k_prep_eval", N, 64, N, ty, m, n, g, xs, ys, as, bs, pm, (S*)pool, sv, 0,
+                  (const S*)nullptr, (S*)nullptr, (uint8_t*)nullptr));
+    } else {
+      if (wide) {  // one lane per output scalar
+        const int W = ty == GS_QUAD ? m : m + n;
+        RC(launch_seg<k_prep_eval_wide<C>>(c, "k_prep_eval.a", N * (size_t)W, 64, N * (size_t)W, W, ty, m, n, (const S*)G,
+                  xs, ys, as, bs, pm, (S*)pool, sv));
+      }
+      if (!wide || ty == GS_QUAD)
+        RC(launch_seg<k_prep_eval<C>>(c, "k_prep_eval", N, 64, N, ty, m, n, (const S*)G, xs, ys, as, bs, pm, (S*)pool, sv,
+                  wide ? 1 : 0, check ? (const S*)target : (const S*)nullptr, check ? (S*)nullptr : (S*)out,
+                  check ? ok : (uint8_t*)nullptr));
+    }
+    if (ty == GS_QUAD) return GS_OK;
+    if (ty == GS_MSMEG1) return eval_msme<F1>(c, sh, N, pm, pool, X, A, target, out, ok, shared);
+    if (ty == GS_MSMEG2) return eval_msme<F2>(c, sh, N, pm, pool, Y, B, target, out, ok, shared);
+    // ---- PPE: W_j, arrays 0 = X, 1 = A.  Shared per-base window tables as in the verifier's Gamma^T c (every base serves
+    // n outputs): planned for large arities while the tables stay below 8 GB, never with "endo" off
+    const double tab8_bytes = (double)N * m * 128.0 * (double)(sizeof(A1) + sizeof(Jac<F1>));
+    const bool tab8 = c->endo && (c->var_tab == 1 || (c->var_tab < 0 && wide && n >= 32 && tab8_bytes <= 8e9));
+    void* w;
+    RC(scratch(c, "eval.w", N * n * Z::G1, &w));
+    {
+      SidePlan sp;
+      sp.points = true;
+      sp.tm = tab8 ? 8 : pick_tm(c, fillN(c, N), m, n, false, n);
+      if (tab8) sp.tab_bases = m;
+      int slot = 0;
+      for (int j = 0; j < n; j++) {
+        const int b = slot;
+        sp.fix.push_back(mkfix(0, 0xFF, 0, 0xFF, 1, j, slot++));  // A_j
+        std::vector<VarTask> terms;
+        for (int i = 0; i < m; i++) terms.push_back(mkvar(pm.GC + i * n + j, 0, i, 0));
+        add_var_terms(sp, terms, slot);
+        sp.red.push_back(mkred(b, slot, b, b, 0, j));
+      }
+      sp.nslots = slot;
+      const ArrTab arrs = arr_tab({{0, X, shared ? 0u : (uint32_t)(m * Z::G1)}, {1, A, (uint32_t)(n * Z::G1)}});
+      const OutTab outs = out_tab(w, (uint32_t)(n * Z::G1));
+      RangeGuard rg("gs.eval.g1");
+      const unsigned masks[4] = {BIT(EI_A), BIT(EI_X), 0u, 0u};
+      RC((run_side<C, F1>(c, ".ev1", N, sp, arrs, (const S*)pool, pm.total, (const A1*)c->tabs->tab16_g1.p, outs, nullptr,
+                          nullptr, nullptr, masks)));
+    }
+    // ---- Miller: one accumulator per equation.  P arrays: 0 = W, 1 = X.  Q arrays: 0 = Y, 1 = B.  All lines stepped
+    RangeGuard rg_m("gs.eval.miller");
+    RC(need(c, BIT(EI_Y) | BIT(EI_B)));
+    std::vector<PairRef> pr;
+    for (int j = 0; j < n; j++) add_pair(pr, 0, j, 0, 0, j);  // (W_j, Y_j)
+    for (int i = 0; i < m; i++) add_pair(pr, 1, i, 0, 1, i);  // (X_i, B_i)
+    const ArrTab parr = arr_tab({{0, w, (uint32_t)(n * Z::G1)}, {1, X, shared ? 0u : (uint32_t)(m * Z::G1)}});
+    const ArrTab qarr = arr_tab({{0, Y, shared ? 0u : (uint32_t)(n * Z::G2)}, {1, B, (uint32_t)(m * Z::G2)}});
+    const std::vector<MillerTask> mt = plan_miller_single(c, fillN(c, N), pr);
+    int ntask = (int)mt.size();
+    // large arities: fold runs of K partials in parallel until the final lane's own serial product is short (as verify)
+    const int K = 8;
+    const int ostride = ntask > 2 * K ? 2 : 1;
+    void* mpart;
+    RC(miller_single(c, "eval", N, mt, parr, qarr, &mpart, ostride));
+    for (int level = 0; ntask > 2 * K; level++) {
+      CellMap cm, cmo;
+      memset(&cm, 0, sizeof cm);
+      memset(&cmo, 0, sizeof cmo);
+      cm.hi[0] = ntask;
+      const int nt_out = (ntask + K - 1) / K;
+      cmo.hi[0] = nt_out;
+      void* folded;
+      RC(scratch(c, level & 1 ? "eval.mfold1" : "eval.mfold0", 2 * N * (size_t)nt_out * sizeof(GT), &folded));
+      const size_t total = N * 4 * (size_t)nt_out;
+      RC(launch_seg<k_cell_fold<C>>(c, "k_cell_fold", total, 64, total, nt_out, ntask, cm, (const GT*)mpart, K, nt_out, cmo,
+                (GT*)folded));
+      mpart = folded;
+      ntask = nt_out;
+    }
+    RangeGuard rg_f("gs.eval.final");
+    if (check) RC(need(c, BIT(EI_TG)));
+    if (coop_lanes(c, fillN(c, N)))
+      return launch_seg<k_final_eval_coop<C>>(c, "k_final_eval.coop", (N + 20) / 21 * 63, 63, N, ntask, ostride,
+                (const GT*)mpart, (const uint8_t*)target, (uint8_t*)out, ok);
+    return launch_seg<k_final_eval<C>>(c, "k_final_eval", N, 64, N, ntask, ostride, (const GT*)mpart,
+              (const uint8_t*)target, (uint8_t*)out, ok);
   }
 
   // product of n internal-form GT elements at `buf` (clobbers buf/tmp); result exported in
@@ -3612,6 +3762,70 @@ int gs_verify_statement(gs_ctx* c, int ty, size_t E, int m, int n, const void* A
                         uint8_t* ok) {
   return batch_host(c, kVerify, {ty, E, m, n, true, {A, B, G, target, xcoms, ycoms, pi, theta, ok}});
 }
+
+// ---- evaluate / check witness: what an equation evaluates to at a witness ------------------------------------------
+// One operation behind the eight entries: gs_eval_* pass target_out (EO_T), gs_check_witness_* pass target (EI_TG) and
+// ok (EO_OK); the other group stays null.
+static const ArrDesc kEvalArrs[] = {
+    {EI_X, lay::X, ARR_IN},      {EI_Y, lay::Y, ARR_IN},          {EI_A, lay::A, ARR_IN},
+    {EI_B, lay::B, ARR_IN},      {EI_G, lay::GAMMA, ARR_IN},      {EI_TG, lay::TARGET, ARR_IN | ARR_OPT},
+    {EO_T, lay::TARGET, ARR_OUT | ARR_OPT}, {EO_OK, lay::OK, ARR_OUT | ARR_OPT}};
+static const int* eval_order(int ty) {
+  // staging order = the order eval() asks for them: Gamma and the scalar arrays, the G1 arrays, the G2 arrays, the target
+  static const int order[4][6] = {{EI_G, EI_A, EI_X, EI_Y, EI_B, EI_TG},
+                                  {EI_G, EI_Y, EI_B, EI_X, EI_A, EI_TG},
+                                  {EI_G, EI_X, EI_A, EI_Y, EI_B, EI_TG},
+                                  {EI_G, EI_X, EI_Y, EI_A, EI_B, EI_TG}};
+  return order[ty];
+}
+static int eval_run(gs_ctx* c, const BatchArgs& a) {
+  const void* const* p = a.p;
+  return DISPATCH(c, eval(c, a.ty, a.N, a.m, a.n, p[EI_X], p[EI_Y], p[EI_A], p[EI_B], p[EI_G], p[EI_TG], a.out(EO_T),
+                          (uint8_t*)a.out(EO_OK), a.shared));
+}
+static const Op kEval = {kEvalArrs, sizeof kEvalArrs / sizeof *kEvalArrs, eval_order, 6, eval_run};
+static BatchArgs eval_args(int ty, size_t N, int m, int n, bool shared, const void* X, const void* Y, const void* A,
+                           const void* B, const void* G, const void* target, void* target_out, uint8_t* ok) {
+  return BatchArgs{ty, N, m, n, shared, {X, Y, A, B, G, target, target_out, ok}};
+}
+// check = a gs_check_witness_* entry (target and ok required), else gs_eval_* (target_out required)
+static int eval_call(gs_ctx* c, const char* fn, bool host, bool check, const BatchArgs& a) {
+  if (c && c->rec) return fail(c, GS_ERR_ARG, (std::string(fn) + " inside a mixed call").c_str());
+  RC(batch_check(c, kEval, a));
+  if (a.N == 0) return GS_OK;
+  if (check ? (!a.p[EI_TG] || !a.p[EO_OK]) : !a.p[EO_T]) return fail(c, GS_ERR_ARG, "null pointer");
+  if (!host) return kEval.run(c, a);
+  // the output does not alias an input (the staged copy would hide it; the device form reads while it writes)
+  const lay::Layout L = layout_of(c, a);
+  const ArrDesc& o = kEvalArrs[check ? 7 : 6];
+  for (const ArrDesc& i : kEvalArrs) {
+    if ((i.flags & ARR_OUT) || !a.p[i.slot]) continue;
+    uintptr_t x = (uintptr_t)a.p[o.slot], y = (uintptr_t)a.p[i.slot];
+    if (x < y + L.bytes[i.arr] && y < x + L.bytes[o.arr])
+      return fail(c, GS_ERR_ARG, (std::string(fn) + ": the output overlaps an input").c_str());
+  }
+  return batch_host_checked(c, kEval, a);
+}
+#define GS_EVAL_ENTRY(NAME, HOST, SHARED)                                                                             \
+  int NAME(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A, const void* B,      \
+           const void* G, void* target_out) {                                                                          \
+    return eval_call(c, #NAME, HOST, false, eval_args(ty, N, m, n, SHARED, X, Y, A, B, G, nullptr, target_out, nullptr)); \
+  }
+#define GS_CHECK_ENTRY(NAME, HOST, SHARED)                                                                            \
+  int NAME(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A, const void* B,      \
+           const void* G, const void* target, uint8_t* ok) {                                                           \
+    return eval_call(c, #NAME, HOST, true, eval_args(ty, N, m, n, SHARED, X, Y, A, B, G, target, nullptr, ok));        \
+  }
+GS_EVAL_ENTRY(gs_eval_batch_dev, false, false)
+GS_EVAL_ENTRY(gs_eval_batch, true, false)
+GS_EVAL_ENTRY(gs_eval_statement_dev, false, true)
+GS_EVAL_ENTRY(gs_eval_statement, true, true)
+GS_CHECK_ENTRY(gs_check_witness_batch_dev, false, false)
+GS_CHECK_ENTRY(gs_check_witness_batch, true, false)
+GS_CHECK_ENTRY(gs_check_witness_statement_dev, false, true)
+GS_CHECK_ENTRY(gs_check_witness_statement, true, true)
+#undef GS_EVAL_ENTRY
+#undef GS_CHECK_ENTRY
 
 // ---- mixed batches: several sub-batches (any types and shapes) in ONE call ----------------------------------------
 // configs[2] of the baseline is a batch of PPE, MSMEG1 and MSMEG2 equations; the reference's Statement is a list of

@@ -1441,6 +1441,216 @@ struct k_and4 {
 }
 };
 
+// ---- equation evaluation (gs_eval_* / gs_check_witness_*): the left-hand sides of statement.rs:17-21 ---------------
+// Fr preparation, one lane per equation.  The Gamma term is folded into the scalars of the OTHER side so that it costs
+// no scalar multiplication of its own:
+//   PPE      Gamma -> canonical (GC); the fold is W_j = A_j + sum_i Gamma_ij X_i in G1, on the Straus lanes
+//   MSMEG1   y_j -> canonical (YC),  c_i = b_i + sum_j Gamma_ij y_j (BC):  value = sum_j y_j A_j + sum_i c_i X_i
+//   MSMEG2   x_i -> canonical (XC),  d_j = a_j + sum_i x_i Gamma_ij (AC):  value = sum_i x_i B_i + sum_j d_j Y_j
+//   QuadEqu  the value itself, sum_j a_j y_j + sum_i x_i c_i, a canonical Montgomery Fr: written to out[e], or (ok
+//            non-null) compared limb by limb with tq[e] -- a target with non-canonical limbs never matches
+// shared_vars: a Statement -- ONE copy of the variables xs / ys for all equations.  folded (QuadEqu, large arities): the
+// c_i are in the pool already, in Montgomery form (k_prep_eval_wide).
+template <class C>
+struct k_prep_eval {
+  static __device__ __forceinline__ void run(size_t e_in, size_t N, int ty, int m, int n, const Fr<C>* G, const Fr<C>* xs,
+                                              const Fr<C>* ys, const Fr<C>* as, const Fr<C>* bs, PoolMap pm, Fr<C>* pool,
+                                              int shared_vars, int folded, const Fr<C>* tq, Fr<C>* out, uint8_t* ok) {
+  size_t e = e_in;
+  if (e >= N) return;
+  typedef Fr<C> S_;
+  const size_t ev = shared_vars ? 0 : e;
+  if (G) G += e * (size_t)m * n;
+  if (xs) xs += ev * m;
+  if (ys) ys += ev * n;
+  if (as) as += e * n;
+  if (bs) bs += e * m;
+  S_* P = pool + e * pm.total;
+  if (ty == 0) {
+    for (int i = 0; i < m * n; i++) P[pm.GC + i] = from_mont(G[i]);
+    return;
+  }
+  if (ty == 1) {
+    for (int j = 0; j < n; j++) P[pm.YC + j] = from_mont(ys[j]);
+    for (int i = 0; i < m; i++) {
+      S_ ci = bs[i];
+      for (int j = 0; j < n; j++) ci = add(ci, mul(G[i * n + j], ys[j]));
+      P[pm.BC + i] = from_mont(ci);
+    }
+    return;
+  }
+  if (ty == 2) {
+    for (int i = 0; i < m; i++) P[pm.XC + i] = from_mont(xs[i]);
+    for (int j = 0; j < n; j++) {
+      S_ dj = as[j];
+      for (int i = 0; i < m; i++) dj = add(dj, mul(xs[i], G[i * n + j]));
+      P[pm.AC + j] = from_mont(dj);
+    }
+    return;
+  }
+  S_ v = fzero<FrM<C>>();
+  for (int j = 0; j < n; j++) v = add(v, mul(as[j], ys[j]));
+  for (int i = 0; i < m; i++) {
+    S_ ci;
+    if (folded) {
+      ci = P[pm.BC + i];
+    } else {
+      ci = bs[i];
+      for (int j = 0; j < n; j++) ci = add(ci, mul(G[i * n + j], ys[j]));
+    }
+    v = add(v, mul(xs[i], ci));
+  }
+  if (ok)
+    ok[e] = eq(v, tq[e]) ? 1 : 0;
+  else
+    out[e] = v;
+}
+};
+// The same for large arities (wide_prep): one lane per OUTPUT SCALAR, W per equation -- n + m for the two MSME types
+// (the canonical variables, then the folded c_i / d_j), m for QuadEqu (the c_i, kept in Montgomery form for
+// k_prep_eval's final sum).  PPE needs only Gamma in canonical form: k_fr_canonical.
+template <class C>
+struct k_prep_eval_wide {
+  static __device__ __forceinline__ void run(size_t g, size_t total, int W, int ty, int m, int n, const Fr<C>* G,
+                                              const Fr<C>* xs, const Fr<C>* ys, const Fr<C>* as, const Fr<C>* bs,
+                                              PoolMap pm, Fr<C>* pool, int shared_vars) {
+  if (g >= total) return;
+  typedef Fr<C> S_;
+  size_t e = g / W;
+  int w = (int)(g % W);
+  const size_t ev = shared_vars ? 0 : e;
+  G += e * (size_t)m * n;
+  if (xs) xs += ev * m;
+  if (ys) ys += ev * n;
+  if (as) as += e * n;
+  if (bs) bs += e * m;
+  S_* P = pool + e * pm.total;
+  if (ty == 2) {
+    if (w < m) {
+      P[pm.XC + w] = from_mont(xs[w]);
+      return;
+    }
+    int j = w - m;
+    S_ dj = as[j];
+    for (int i = 0; i < m; i++) dj = add(dj, mul(xs[i], G[i * n + j]));
+    P[pm.AC + j] = from_mont(dj);
+    return;
+  }
+  if (ty == 1 && w < n) {
+    P[pm.YC + w] = from_mont(ys[w]);
+    return;
+  }
+  int i = ty == 1 ? w - n : w;
+  S_ ci = bs[i];
+  for (int j = 0; j < n; j++) ci = add(ci, mul(G[i * n + j], ys[j]));
+  P[pm.BC + i] = ty == 1 ? from_mont(ci) : ci;
+}
+};
+
+// k_red for outputs of ONE point each (the evaluated MSME value, the W_j of a PPE): up to K consecutive outputs per lane
+// behind one shared inversion; output t.out_idx of array t.out_arr is a point index.  Only the run [b0, e0) of a
+// RedTask is read.
+template <class C, class F>
+struct k_red_pt {
+  static __device__ __forceinline__ void run(size_t g, size_t total, int ntask, const RedTask* tasks, const Jac<F>* part,
+                                              int nslots, OutTab outs, int K) {
+  if (g >= total) return;
+  const int nl = (ntask + K - 1) / K;  // lanes per equation
+  size_t e = g / nl;
+  int t0 = (int)(g % nl) * K, nt = ntask - t0 < K ? ntask - t0 : K;
+  const Jac<F>* P = part + e * nslots;
+  Jac<F> s[RED_K];
+  F pre[RED_K];  // pre[i] = z_0 ... z_(i-1) (identities count as 1)
+  F acc = one_of<F>();
+  for (int k = 0; k < nt; k++) {
+    RedTask t = tasks[t0 + k];
+    Jac<F> s0 = P[t.b0];
+    for (uint32_t i = t.b0 + 1; i < t.e0; i++) jac_add(s0, s0, P[i]);
+    s[k] = s0;
+    pre[k] = acc;
+    if (!is_zero_limbs(s0.z)) acc = mul(acc, s0.z);
+  }
+  F suf = inv(acc);  // 1 / (z_0 ... z_(nt - 1))
+  for (int i = nt - 1; i >= 0; i--) {
+    RedTask t = tasks[t0 + i];
+    Aff<F> a;
+    F zi = mul(suf, pre[i]);  // 1 / z_i
+    if (!is_zero_limbs(s[i].z)) suf = mul(suf, s[i].z);
+    jac_to_aff_zinv(a, s[i], zi);  // (identity -> (0, 0), zi unused)
+    aff_store<C>(outs.base[t.out_arr] + e * outs.stride[t.out_arr] + (size_t)t.out_idx * AFFB(C, F), a);
+  }
+}
+};
+
+// The end of a PPE evaluation: FE(product of the equation's Miller partials) is WRITTEN in boundary form to out[e], or
+// (ok non-null) compared with target[e].  The comparison is on the boundary limbs themselves: the value's are canonical,
+// so a target with non-canonical limbs never matches (f12_from_boundary + f12_eq would reduce it first).
+template <class C>
+GS_HD_NOINLINE void eval_gt_finish(const Fp12<C>& r, size_t e, const uint8_t* target, uint8_t* out, uint8_t* ok) {
+  if (!ok) {
+    f12_to_boundary<C>(reinterpret_cast<BFq<C>*>(out) + 12 * e, r);
+    return;
+  }
+  BFq<C> x[12];
+  f12_to_boundary<C>(x, r);
+  const BFq<C>* t = reinterpret_cast<const BFq<C>*>(target) + 12 * e;
+  uint32_t o = 0;
+  for (int i = 0; i < 12; i++)
+    for (int j = 0; j < C::N; j++) o |= x[i].w[j] ^ t[i].w[j];
+  ok[e] = o == 0 ? 1 : 0;
+}
+// partials of equation e: mpart[ostride * (e * ntask + i)], i < ntask (ostride 2: the layout k_cell_fold leaves)
+template <class C>
+GS_HD_NOINLINE void eval_product(Fp12<C>& f, const Fp12<C>* mpart, size_t e, int ntask, int ostride) {
+  f = mpart[(size_t)ostride * (e * ntask)];
+  for (int i = 1; i < ntask; i++) f12_mul(f, f, mpart[(size_t)ostride * (e * ntask + i)]);
+}
+// ONE cell per equation; the body of k_final / k_final_coop otherwise
+template <class C>
+struct k_final_eval {
+  static __device__ __forceinline__ void run(size_t e_in, size_t N, int ntask, int ostride, const Fp12<C>* mpart,
+                                              const uint8_t* target, uint8_t* out, uint8_t* ok) {
+  size_t e = e_in;
+  if (e >= N) return;
+  Fp12<C> f;
+  eval_product(f, mpart, e, ntask, ostride);
+  Fp12<C> r;
+  final_exp(r, f);
+  eval_gt_finish<C>(r, e, target, out, ok);
+}
+};
+// 3-lane group per equation (blockDim.x == 63: one wave = 21 groups; idle groups of the last wave shadow the last equation
+// so that every lane reaches the shuffles)
+template <class C>
+struct k_final_eval_coop {
+  static __device__ __forceinline__ void run(size_t gt, size_t N, int ntask, int ostride, const Fp12<C>* mpart,
+                                              const uint8_t* target, uint8_t* out, uint8_t* ok) {
+  int lane = (int)(gt % 63), j = lane % 3;
+  size_t e = (gt / 63) * 21 + lane / 3;
+  bool live = e < N;
+  if (!live) e = N - 1;
+  Fp12<C> f;
+  eval_product(f, mpart, e, ntask, ostride);
+  Fp12<C> r;
+  CoopWave xw{lane - j};
+  ExpXCoop<C, CoopWave> ex{j, &xw};
+  final_exp_with(r, f, ex);
+  if (live && j == 0) eval_gt_finish<C>(r, e, target, out, ok);
+}
+};
+// ok[e] = (the evaluated point e == target e) on their boundary words: the value is normalised affine with canonical
+// limbs (the identity all-zero), so equality as elements is equality of words and a non-canonical target never matches
+struct k_eval_cmp {
+  static __device__ __forceinline__ void run(size_t e_in, size_t N, int words, const uint32_t* val, const uint32_t* tgt,
+                                              uint8_t* ok) {
+  size_t e = e_in;
+  if (e >= N) return;
+  uint32_t o = 0;
+  for (int w = 0; w < words; w++) o |= val[e * words + w] ^ tgt[e * words + w];
+  ok[e] = o == 0 ? 1 : 0;
+}
+};
+
 // E::multi_pairing per row: k pairs -> Miller product -> final exponentiation
 template <class C>
 __global__ void __launch_bounds__(64, GS_WPE) k_multi_pairing(size_t n, int k, const uint8_t* P, const uint8_t* Q,

@@ -8,6 +8,8 @@ top of the C ABI (same names, argument meaning and error behaviour):
         .commit_and_prove(xvars, yvars, crs, rng) -> CProof                src/prover/prove.rs:29-52
         .prove(xvars, yvars, xcoms, ycoms, crs, rng) -> EquProof
         .verify(com_proof, crs) -> bool                                    src/verifier.rs:18-21
+        .evaluate(xvars, yvars, crs) -> target, .is_satisfied_by(xvars, yvars, crs) -> bool, <Type>.from_witness(..)
+                                                                           (new) the left-hand side at a witness
     rerandomize(equ, com_proof, crs, rng) -> CProof                      (new) fresh commitments and proof, no witness
     generate_crs_with_key -> (CRS, key), extract(commit, crs, key)        (new) open commitments with the binding key
     extract_scalars(commit, crs, key, bits, log2_table=None)              (new) committed scalars < 2^bits back themselves
@@ -210,6 +212,36 @@ class _Equation:
         assert len(self.a_consts) == n, "a_consts.len() == yvars.len()"
         assert len(self.b_consts) == m, "b_consts.len() == xvars.len()"
         assert len(self.gamma) == m and all(len(row) == n for row in self.gamma), "gamma is m x n"
+
+    # -- evaluation (the left-hand sides of statement.rs:17-21) ---------------
+    def evaluate(self, xvars, yvars, crs):
+        """What the equation evaluates to at the witness (gs_eval_batch): a GT / G1 / G2 / Fr value in the limbs `target`
+        is held in -- the target that makes (xvars, yvars) a satisfying witness.  The reference leaves this sum to the
+        caller (tests/prover.rs:50-52 writes it out with arkworks)."""
+        m, n = len(xvars), len(yvars)
+        assert m >= 1 and n >= 1
+        self._check_statement_shape(m, n)
+        out = crs.engine.eval_batch(self.TYPE, 1, m, n, _cat(xvars, 0), _cat(yvars, 0), _cat(self.a_consts, 0),
+                                    _cat(self.b_consts, 0), _flat_mat(self.gamma))
+        return out[0].view(np.uint64).copy()
+
+    def is_satisfied_by(self, xvars, yvars, crs):
+        """Does the witness satisfy the equation -- does it evaluate to `target` (gs_check_witness_batch)?  What
+        Provable::prove never checks: a proof made from a wrong witness fails only at the verifier."""
+        m, n = len(xvars), len(yvars)
+        assert m >= 1 and n >= 1
+        self._check_statement_shape(m, n)
+        ok = crs.engine.check_witness_batch(self.TYPE, 1, m, n, _cat(xvars, 0), _cat(yvars, 0), _cat(self.a_consts, 0),
+                                            _cat(self.b_consts, 0), _flat_mat(self.gamma),
+                                            np.asarray(self.target, dtype=np.uint64).reshape(-1))
+        return bool(ok[0])
+
+    @classmethod
+    def from_witness(cls, a_consts, b_consts, gamma, xvars, yvars, crs):
+        """The equation with these constants whose target is its value at (xvars, yvars): true by construction."""
+        equ = cls(a_consts, b_consts, gamma, None)
+        equ.target = equ.evaluate(xvars, yvars, crs)
+        return equ
 
     # -- Provable ---------------------------------------------------------
     def _kxky(self):
@@ -437,6 +469,30 @@ class Statement:
         pis, ths = _split(out["pi"], E * kx), _split(out["theta"], E * ky)
         proofs = [EquProof(pis[e * kx:(e + 1) * kx], ths[e * ky:(e + 1) * ky], self.TYPE, Ts[e]) for e in range(E)]
         return CProof(xcoms, ycoms, proofs)
+
+    def _witness_arrays(self, xvars, yvars):
+        """(m, n, X, Y, A, B, Gamma as gs_eval_statement takes them) after the shape checks"""
+        m, n = len(xvars), len(yvars)
+        assert m >= 1 and n >= 1
+        for equ in self.equations:
+            equ._check_statement_shape(m, n)
+        cat = np.concatenate
+        return m, n, (_cat(xvars, 0), _cat(yvars, 0), cat([_cat(e.a_consts, 0) for e in self.equations]),
+                      cat([_cat(e.b_consts, 0) for e in self.equations]), cat([_flat_mat(e.gamma) for e in self.equations]))
+
+    def evaluate(self, xvars, yvars, crs):
+        """[the value of every equation at the shared witness] (gs_eval_statement): the targets that make it satisfying"""
+        m, n, arrays = self._witness_arrays(xvars, yvars)
+        out = crs.engine.eval_statement(self.TYPE, len(self.equations), m, n, *arrays)
+        return [row.view(np.uint64).copy() for row in out]
+
+    def is_satisfied_by(self, xvars, yvars, crs):
+        """[bool per equation]: does the shared witness satisfy it (gs_check_witness_statement); the statement holds iff
+        all are true"""
+        m, n, arrays = self._witness_arrays(xvars, yvars)
+        target = np.concatenate([np.asarray(e.target, dtype=np.uint64).reshape(-1) for e in self.equations])
+        ok = crs.engine.check_witness_statement(self.TYPE, len(self.equations), m, n, *arrays, target)
+        return [bool(v) for v in ok]
 
     def verify(self, com_proof, crs):
         """[bool per equation]; the statement holds iff all are true"""

@@ -12,6 +12,9 @@
  *   gs_verify_batch_rlc_locate <- (new) the same check with the product tree kept and descended: which proofs are bad
  *   gs_rerandomize_batch   <- (new) rerandomization of commitments and proofs without the witness (the same
  *                             algebra as src/prover/prove.rs:92-171,195-274,298-379,409-488 applied to fresh randomness)
+ *   gs_eval_batch / gs_check_witness_batch <- (new) the left-hand sides of src/statement.rs:17-21 at a witness: an
+ *                             equation's target, and whether a witness satisfies it (tests/prover.rs:50-52,87-90,125-128,
+ *                             160-162 write the same sums by hand with arkworks)
  *   gs_mat_left_mul_com1/2 <- src/data_structures.rs:696-742 (Mat::left_mul on Matrix<Com1/Com2>)
  *   gs_pairing_sum         <- src/data_structures.rs:494-502 (ComT::pairing_sum)
  *   gs_set_crs             <- consumes src/generator.rs:35-42 (struct CRS)
@@ -375,6 +378,60 @@ int gs_verify_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const
 int gs_verify_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B, const void* Gamma,
                         const void* target, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
                         uint8_t* ok);
+/* ---- evaluate: what an equation evaluates to at a witness, and whether a witness satisfies it -----------------------
+ * Every equation carries a target; a statement builder computes it from the witness before anything can be proved, and a
+ * prover wants to know that its witness satisfies the equation BEFORE it pays for a proof that the verifier rejects
+ * (Provable::prove does not check).  Layouts are those of gs_prove_batch / gs_verify_batch: X[N][m], Y[N][n], A[N][n],
+ * B[N][m], Gamma[N][m][n], target[N], ok[N]; the _statement forms take ONE copy of X[m], Y[n] for all E equations, exactly
+ * as gs_prove_statement does.  The value of equation e (the left-hand sides of src/statement.rs:17-21):
+ *   GS_PPE    : prod_j e(A_j, Y_j) * prod_i e(X_i, B_i) * prod_ij e(X_i, Y_j)^Gamma_ij   a canonical GT element in boundary
+ *               form: for the same pairs the bytes gs_multi_pairing_batch writes, and what a verifying PPE target equals
+ *   GS_MSMEG1 : sum_j y_j A_j + sum_i b_i X_i + sum_ij Gamma_ij y_j X_i   normalised affine G1, the identity all-zero bytes
+ *   GS_MSMEG2 : sum_j a_j Y_j + sum_i x_i B_i + sum_ij Gamma_ij x_i Y_j   the same in G2
+ *   GS_QUAD   : sum_j a_j y_j + sum_i x_i b_i + sum_ij x_i Gamma_ij y_j   a canonical Montgomery Fr
+ * gs_eval_*: target_out[e] = that value.  gs_check_witness_*: ok[e] = 1 iff the value of equation e equals target[e] AS AN
+ * ELEMENT; the comparison is on the boundary limbs of the canonical value, so a target with non-canonical limbs never
+ * matches.
+ * How it is computed: the Gamma term is FOLDED so that it costs no pairing and no scalar multiplication
+ * of its own -- PPE: W_j = A_j + sum_i Gamma_ij X_i in G1 (n short sums over the same m bases), then m + n Miller pairs
+ * and ONE final exponentiation per equation (a 4 x 4 PPE: 8 pairs and one, where gs_verify_batch pays 40 and four); MSMEG1 / MSMEG2:
+ * one sum of m + n terms with the scalars c_i = b_i + sum_j Gamma_ij y_j (d_j = a_j + sum_i x_i Gamma_ij) folded in Fr;
+ * QuadEqu: one lane of Fr arithmetic per equation.
+ * A CRS must be installed (GS_ERR_NOCRS) although none of its elements is read.  Shapes and errors as gs_prove_batch;
+ * N == 0 is a no-op.  The host forms return GS_ERR_ARG when the output overlaps an input; for the _dev forms that is the
+ * caller's contract.  The _dev forms only enqueue on the context's stream.  The calls are refused inside a mixed call
+ * (GS_ERR_ARG).  The multi-GPU handles (gs_multi_*) have NO counterpart: use a shard's context (gs_multi_ctx).  Points
+ * outside the prime-order subgroups fall under the rule at the top of this file; "endo" = 0 is followed (the variable-base
+ * lanes run plain, "k_var.plain").  "var_tm", "var_mo", "var_w", "var_w2", "var_ws_lanes", "red_k", "miller_ch" and
+ * "coop_fe" act as they do elsewhere, "var_tab" = 1 puts the PPE's W_j on shared window tables of the X_i; "line_tables"
+ * has nothing to act on: no argument is a CRS element, every line is stepped.
+ * WHEN TO CALL IT (tools/eval_rate.py, profiles/eval/rate.json, DESIGN.md 6.8: BLS12-381, 4 x 4, one MI355X, device-
+ * resident, median of 7, entries alternating), ms per call at N = 2^12 / 2^14 / 2^16 -- PPE: this entry 14.4 / 23.2 / 62.1,
+ * gs_verify_batch_dev on the same batch 20.6 / 55.5 / 197.4, gs_prove_batch_dev 8.4 / 19.6 / 64.9, gs_multi_pairing_batch_dev
+ * on 8 arbitrary pairs per row (no Gamma work) 42.3 / 43.0 / 48.5; BN254 PPE at 2^16: 44.2 against 143.9 (verify); MSMEG1:
+ * 1.9 / 2.8 / 8.3 against 19.7 / 49.4 / 185.4 (verify).  gs_check_witness_* costs what gs_eval_* costs.  Call
+ * gs_check_witness_* before gs_prove_batch whenever the witness is not known to be good: at 2^16 it costs 0.24 of the
+ * prove + verify a bad witness would waste (PPE; 0.04 for MSMEG1) and names the failing equations.  For targets, call
+ * gs_eval_* rather than pairing the Gamma term out by hand: below ~2^15 rows it is also faster than gs_multi_pairing_batch on
+ * the m + n pairs alone (that entry runs one lane per row), above it it costs the Gamma sum more (13.5 of 62.1 ms at 2^16).
+ * Kernel profile names: "k_prep_eval[.a]", "k_fix.ev1" (the PPE's addends A_j), "k_var*.ev1|.ev2", "k_red.ev1|.ev2",
+ * "k_miller.eval" (gs_prof_get_work: pairs), "k_cell_fold", "k_final_eval[.coop]", "k_eval_cmp" (the point types' check). */
+int gs_eval_batch_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                      const void* B, const void* Gamma, void* target_out);
+int gs_eval_batch(gs_ctx*, int equ_type, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                  const void* B, const void* Gamma, void* target_out);
+int gs_eval_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y, const void* A,
+                          const void* B, const void* Gamma, void* target_out);
+int gs_eval_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y, const void* A,
+                      const void* B, const void* Gamma, void* target_out);
+int gs_check_witness_batch_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                               const void* B, const void* Gamma, const void* target, uint8_t* ok);
+int gs_check_witness_batch(gs_ctx*, int equ_type, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                           const void* B, const void* Gamma, const void* target, uint8_t* ok);
+int gs_check_witness_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y,
+                                   const void* A, const void* B, const void* Gamma, const void* target, uint8_t* ok);
+int gs_check_witness_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y, const void* A,
+                               const void* B, const void* Gamma, const void* target, uint8_t* ok);
 /* ---- mixed batches and mixed-type Statements: several sub-batches in ONE call ------------------------------------
  * configs[2] of the baseline mixes PPE, MSMEG1 and MSMEG2 equations; the reference's Statement is a list of equations
  * of ANY type over one list of variables (src/statement.rs:24-28,109).  A part is a homogeneous sub-batch (type, N, m,

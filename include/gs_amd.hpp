@@ -401,6 +401,29 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     for (const auto& row : gamma) assert_eq(row.size(), n, "gamma[i].len() == yvars.len()");
   }
 
+  // (new) What the equation evaluates to at a witness -- the left-hand side of statement.rs:17-21 (gs_eval_batch): the
+  // target that makes (xvars, yvars) a satisfying witness.  The reference leaves this sum to the caller
+  // (tests/prover.rs:50-52 writes it out with arkworks).
+  AT evaluate(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const CRS& crs) const {
+    const Ctx& cx = *crs.ctx;
+    WitnessArrays w = witness_arrays(xvars, yvars, cx);
+    AT out{Bytes(target_size(cx))};
+    cx.chk(gs_eval_batch(cx.c, (int)TYPE, 1, (int)w.m, (int)w.n, w.X.data(), w.Y.data(), w.A.data(), w.B.data(),
+                         w.G.data(), out.v.data()));
+    return out;
+  }
+  // (new) Does the witness satisfy the equation: does it evaluate to `target` (gs_check_witness_batch)?  What
+  // Provable::prove never checks -- a proof made from a wrong witness fails only at the verifier.
+  bool is_satisfied_by(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const CRS& crs) const {
+    const Ctx& cx = *crs.ctx;
+    WitnessArrays w = witness_arrays(xvars, yvars, cx);
+    assert_eq(target.v.size(), target_size(cx), "target size");
+    uint8_t ok = 0;
+    cx.chk(gs_check_witness_batch(cx.c, (int)TYPE, 1, (int)w.m, (int)w.n, w.X.data(), w.Y.data(), w.A.data(),
+                                  w.B.data(), w.G.data(), target.v.data(), &ok));
+    return ok == 1;
+  }
+
   template <class Rng>
   CProof commit_and_prove(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const CRS& crs, Rng& rng) const {
     Commit1 xcoms = batch_commit_x(xvars, crs, rng);
@@ -573,6 +596,29 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
                                   xc.data(), yc.data(), pi.data(), th.data(), rho.data(), nullptr, &ok));
     return ok == 1;
   }
+
+ private:
+  static size_t target_size(const Ctx& cx) {
+    return TYPE == EquType::PairingProduct ? cx.sz[4] : TYPE == EquType::MultiScalarG1 ? cx.sz[2]
+           : TYPE == EquType::MultiScalarG2 ? cx.sz[3] : cx.sz[1];
+  }
+  // the five input arrays of gs_eval_batch / gs_check_witness_batch for ONE equation, every length checked
+  struct WitnessArrays {
+    size_t m, n;
+    Bytes X, Y, A, B, G;
+  };
+  WitnessArrays witness_arrays(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const Ctx& cx) const {
+    WitnessArrays w{xvars.size(), yvars.size(), cat(xvars), cat(yvars), cat(a_consts), cat(b_consts), cat(gamma)};
+    if (w.m == 0 || w.n == 0) throw Panic("index out of bounds: empty variable list");
+    check_statement_shape(w.m, w.n);
+    const size_t sx = is_scalar<A1>::value ? cx.sz[1] : cx.sz[2], sy = is_scalar<A2>::value ? cx.sz[1] : cx.sz[3];
+    assert_eq(w.X.size(), w.m * sx, "xvars bytes");
+    assert_eq(w.Y.size(), w.n * sy, "yvars bytes");
+    assert_eq(w.A.size(), w.n * sx, "a_consts bytes");
+    assert_eq(w.B.size(), w.m * sy, "b_consts bytes");
+    assert_eq(w.G.size(), w.m * w.n * cx.sz[1], "gamma bytes");
+    return w;
+  }
 };
 
 using PPE = Equation<G1Affine, G2Affine, GT, EquType::PairingProduct>;
@@ -691,7 +737,60 @@ class Statement {
     return out;
   }
 
+  // (new) The value of every equation at the shared witness, in the statement's order (gs_eval_statement, one call per
+  // equation type): the bytes of the GT / G1 / G2 / Fr target that makes the witness satisfy that equation.
+  std::vector<Bytes> evaluate(const StatementVars& v, const CRS& crs) const { return eval_parts(v, crs, false); }
+  // (new) Per equation: does the shared witness satisfy it, i.e. evaluate to its target (gs_check_witness_statement)?
+  // The statement holds iff all are true.
+  std::vector<bool> is_satisfied_by(const StatementVars& v, const CRS& crs) const {
+    std::vector<bool> ok;
+    for (const Bytes& b : eval_parts(v, crs, true)) ok.push_back(b.at(0) == 1);
+    return ok;
+  }
+
  private:
+  // evaluate (check false: the value of every equation) or check (true: one byte per equation), one call per type
+  std::vector<Bytes> eval_parts(const StatementVars& v, const CRS& crs, bool check) const {
+    const Ctx& cx = *crs.ctx;
+    std::vector<Bytes> out(items.size());
+    Bytes Xg = cat(v.xg), Yg = cat(v.yg), Xs = cat(v.xs), Ys = cat(v.ys);
+    for (Part& p : parts()) {
+      const bool xg = xgroup(p.ty), yg = ygroup(p.ty);
+      const size_t m = xg ? v.xg.size() : v.xs.size(), n = yg ? v.yg.size() : v.ys.size();
+      if (m == 0 || n == 0) throw Panic("index out of bounds: empty variable list");
+      const size_t tsz = p.ty == EquType::PairingProduct ? cx.sz[4] : p.ty == EquType::MultiScalarG1 ? cx.sz[2]
+                         : p.ty == EquType::MultiScalarG2 ? cx.sz[3] : cx.sz[1];
+      auto app = [](Bytes& d, const Bytes& s) { d.insert(d.end(), s.begin(), s.end()); };
+      for (size_t i : p.idx) {
+        check_item(items[i], m, n);
+        if (check) assert_eq(items[i].target.size(), tsz, "target size");
+        app(p.A, items[i].A);
+        app(p.B, items[i].B);
+        app(p.G, items[i].G);
+        if (check) app(p.target, items[i].target);
+      }
+      const size_t E = p.idx.size(), sx = xg ? cx.sz[2] : cx.sz[1], sy = yg ? cx.sz[3] : cx.sz[1];
+      const Bytes &X = xg ? Xg : Xs, &Y = yg ? Yg : Ys;
+      assert_eq(X.size(), m * sx, "xvars bytes");
+      assert_eq(Y.size(), n * sy, "yvars bytes");
+      assert_eq(p.A.size(), E * n * sx, "a_consts bytes");
+      assert_eq(p.B.size(), E * m * sy, "b_consts bytes");
+      assert_eq(p.G.size(), E * m * n * cx.sz[1], "gamma bytes");
+      if (check) {
+        p.ok.assign(E, 0);
+        cx.chk(gs_check_witness_statement(cx.c, (int)p.ty, E, (int)m, (int)n, X.data(), Y.data(), p.A.data(),
+                                          p.B.data(), p.G.data(), p.target.data(), p.ok.data()));
+        for (size_t e = 0; e < E; e++) out[p.idx[e]] = Bytes{p.ok[e]};
+      } else {
+        Bytes val(E * tsz);
+        cx.chk(gs_eval_statement(cx.c, (int)p.ty, E, (int)m, (int)n, X.data(), Y.data(), p.A.data(), p.B.data(),
+                                 p.G.data(), val.data()));
+        for (size_t e = 0; e < E; e++) out[p.idx[e]].assign(val.begin() + e * tsz, val.begin() + (e + 1) * tsz);
+      }
+    }
+    return out;
+  }
+  void check_item(const Item& it, size_t m, size_t n) const { check(it, m, n); }
   // the verifier's arrays of every part (one per equation type, shared commitments), after the length checks
   struct VerifyArrays {
     std::vector<Part> ps;
