@@ -45,6 +45,8 @@ SYMBOLS = [
     "gs_eval_batch_dev", "gs_eval_batch", "gs_eval_statement_dev", "gs_eval_statement",
     "gs_check_witness_batch_dev", "gs_check_witness_batch", "gs_check_witness_statement_dev",
     "gs_check_witness_statement",
+    "gs_set_simulation_key", "gs_simulate_batch_dev", "gs_simulate_batch", "gs_simulate_statement_dev",
+    "gs_simulate_statement",
 ]
 # (gs_ctx*, int equ_type, size_t N, int m, int n, X, Y, A, B, Gamma, ...): gs_eval_* end in target_out, gs_check_witness_*
 # in target, ok
@@ -357,6 +359,57 @@ class Engine:
         (gs_rerandomize_statement)."""
         return self._rerand_host("gs_rerandomize_statement", True, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
                                  R, S, T)
+
+    # -- simulation with the hiding CRS's trapdoor ---------------------------------------------------------------
+    def set_simulation_key(self, key):
+        """Install the trapdoor (t1, t2) of the installed hiding CRS: two Montgomery Fr (gs_set_simulation_key); None
+        forgets it.  A wrong key or a binding CRS raises GsError code 3 and installs nothing."""
+        if key is None:
+            self._chk(self.lib.gs_set_simulation_key(self.ctx, _p(None)))
+            return
+        key = np.ascontiguousarray(key).view(np.uint8).reshape(-1)
+        _need("gs_set_simulation_key", [("key", key, 2 * self.FR)])
+        self._chk(self.lib.gs_set_simulation_key(self.ctx, _p(key)))
+
+    def _simulate(self, fn, ty, N, m, n, A, B, Gamma, target, Rc, Sc, Tf, outs=None, want_coms=True):
+        """gs_simulate_*, host and _dev forms: the byte-length checks of _check_prove (Rc, Sc, Tf are sized like R, S,
+        T) before the ABI is crossed, then the call.  A host form allocates its outputs, a _dev form takes them in
+        `outs` = (xcoms, ycoms, pi, theta), the first two may be None."""
+        dev, shared = fn.endswith("_dev"), "_statement" in fn
+        ins = (A, B, Gamma, target, Rc, Sc, Tf)
+        if any(a is None for a in ins):
+            raise GsError(3, "%s: every input array is required" % fn)
+        if not dev:
+            ins = tuple(_u8(a) for a in ins)
+        want = self._check(fn, ty, N, m, n, shared, **dict(zip(("A", "B", "Gamma", "target", "R", "S", "T"), ins)))
+        if dev:
+            if outs is None or outs[2] is None or outs[3] is None:
+                raise GsError(3, "%s: pi and theta are required" % fn)
+        else:
+            outs = (self._out(want["xcoms"]) if want_coms else None, self._out(want["ycoms"]) if want_coms else None,
+                    self._out(want["pi"]), self._out(want["theta"]))
+        self._check(fn, ty, N, m, n, shared, **dict(zip(("xcoms", "ycoms", "pi", "theta"), outs)))
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, ctypes.c_size_t(N), m, n, *[_p(a) for a in ins + tuple(outs)]))
+        return dict(zip(("xcoms", "ycoms", "pi", "theta"), outs))
+
+    def simulate_batch(self, ty, N, m, n, A, B, Gamma, target, Rc, Sc, Tf, want_coms=True):
+        """Commitments and proofs of N equations WITHOUT a witness, from the installed trapdoor (gs_simulate_batch):
+        Rc[N][m][kx], Sc[N][n][ky] are the commitments' coordinates in u / v, Tf[N][ky][kx] the free proof scalars, all
+        uniform, fresh and secret.  GS_PPE is refused."""
+        return self._simulate("gs_simulate_batch", ty, N, m, n, A, B, Gamma, target, Rc, Sc, Tf, want_coms=want_coms)
+
+    def simulate_statement(self, ty, E, m, n, A, B, Gamma, target, Rc, Sc, Tf, want_coms=True):
+        """E equations over ONE simulated commitment set Rc[m][kx], Sc[n][ky]; Tf[E][ky][kx] (gs_simulate_statement)."""
+        return self._simulate("gs_simulate_statement", ty, E, m, n, A, B, Gamma, target, Rc, Sc, Tf,
+                              want_coms=want_coms)
+
+    def simulate_batch_dev(self, ty, N, m, n, A, B, Gamma, target, Rc, Sc, Tf, xcoms, ycoms, pi, theta):
+        """Device form (torch tensors): only enqueues on the context's stream."""
+        self._simulate("gs_simulate_batch_dev", ty, N, m, n, A, B, Gamma, target, Rc, Sc, Tf, (xcoms, ycoms, pi, theta))
+
+    def simulate_statement_dev(self, ty, E, m, n, A, B, Gamma, target, Rc, Sc, Tf, xcoms, ycoms, pi, theta):
+        self._simulate("gs_simulate_statement_dev", ty, E, m, n, A, B, Gamma, target, Rc, Sc, Tf,
+                       (xcoms, ycoms, pi, theta))
 
     def set_extraction_key(self, key):
         """Install the binding key (a1, a2) of the installed CRS: two Montgomery Fr (gs_set_extraction_key); None

@@ -144,6 +144,10 @@ struct gs_ctx {
   // without the endomorphism, G2 likewise.  They are the secret: zeroed when the key goes (clear_extraction_key).
   DevBuf xkey;
   bool have_xkey = false;
+  // simulation trapdoor (gs_set_simulation_key): t1, t2 as two Montgomery Fr in device memory, read by k_prep_sim alone.
+  // A secret like the binding key: zeroed when the key goes (clear_simulation_key).
+  DevBuf skey;
+  bool have_skey = false;
   // baby-step tables of gs_dlog_prepare, one per group ([0] G1, [1] G2): public data, not tied to the CRS
   struct DlogTab {
     DevBuf slots;  // 2^(log2_table + 1) x u64
@@ -564,6 +568,7 @@ enum { PI_X = 0, PI_Y, PI_A, PI_B, PI_G, PI_R, PI_S, PI_T, PO_XC, PO_YC, PO_PI, 
 enum { VI_A = 0, VI_B, VI_G, VI_TG, VI_XC, VI_YC, VI_PI, VI_TH, VO_OK };                            // verify
 enum { RI_A = 0, RI_B, RI_G, RI_R, RI_S, RI_T, RI_XC, RI_YC, RI_PI, RI_TH, RO_XC, RO_YC, RO_PI, RO_TH };  // rerandomize
 enum { EI_X = 0, EI_Y, EI_A, EI_B, EI_G, EI_TG, EO_T, EO_OK };                                      // evaluate / check witness
+enum { SI_A = 0, SI_B, SI_G, SI_TG, SI_R, SI_S, SI_T, SO_XC, SO_YC, SO_PI, SO_TH };                 // simulate
 #define BIT(i) (1u << (i))
 
 // the batch size the lane-shape planners should fill the chip for: the part's own, or (mixed calls, whose parts'
@@ -1930,6 +1935,85 @@ template <class C> struct Impl {
     return side((F2*)nullptr, N, true, true, ".rg2");
   }
 
+  // simulation with the hiding CRS's trapdoor (t1, t2: W1 = t1 u0, W2 = t2 v0), MSMEG1 / MSMEG2 / QuadEqu, no witness:
+  //   c_i = sum_a Rc_ia u_a,  d_j = sum_b Sc_jb v_b                      (commitments to nothing in particular)
+  //   QuadEqu: theta = Tf u0, pi = OM v0
+  //   MSMEG1:  pi_k = Tf[0][k] v0,  theta = (O, V) + OM_0 u0 + OM_1 u1,  V = sum_j Sc_j A_j - t2 T
+  //   MSMEG2:  theta_l = Tf[l][0] u0,  pi = (O, V) + OM_0 v0 + OM_1 v1,  V = sum_i Rc_i B_i - t1 T
+  // (OM: k_prep_sim).  Every output component is one k_fix lane; V is n + 1 (m + 1) variable-base terms behind the
+  // fixed-base lane of component 1.  The pool holds -t and products with t: it is zeroed behind its last reader.
+  // shared: a Statement -- ONE copy of Rc, Sc (stride 0); the commitments are written once, then the N proofs.
+  static int simulate(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G,
+                      const void* tg, const void* Rc, const void* Sc, const void* Tf, void* xcoms, void* ycoms,
+                      void* pi, void* theta, bool shared) {
+    const Shape sh(ty, m, n);
+    const PoolMap pm = pool_layout({{&PoolMap::RC, m * sh.kx}, {&PoolMap::SC, n * sh.ky}, {&PoolMap::TC, sh.ky * sh.kx},
+                                    {&PoolMap::OM, 2}, {&PoolMap::NT, 1}});
+    void* pool;
+    const size_t pool_bytes = N * pm.total * sizeof(S);
+    RC(scratch(c, "sim.pool", pool_bytes, &pool));
+    struct PoolWipe {  // whatever happens below: on the stream, after the kernels enqueued so far
+      gs_ctx* c;
+      void* p;
+      size_t bytes;
+      ~PoolWipe() { hipMemsetAsync(p, 0, bytes, c->stream); }
+    } wipe{c, pool, pool_bytes};
+    RangeGuard rg_all("gs.simulate");
+    RC(need(c, BIT(SI_G) | BIT(SI_R) | BIT(SI_S) | BIT(SI_T) | (sh.xg ? 0u : BIT(SI_A)) | (sh.yg ? 0u : BIT(SI_B)) |
+                   (ty == GS_QUAD ? BIT(SI_TG) : 0u)));
+    RC(launch_seg<k_prep_sim<C>>(c, "k_prep_sim", N, 64, N, ty, m, n, (const S*)G, sh.xg ? (const S*)nullptr : (const S*)A,
+                                 sh.yg ? (const S*)nullptr : (const S*)B, ty == GS_QUAD ? (const S*)tg : (const S*)nullptr,
+                                 (const S*)Rc, (const S*)Sc, (const S*)Tf, (const S*)c->skey.p, pm, (S*)pool,
+                                 shared ? 1 : 0));
+    // one side over NN equations: the commitments (coms non-null) and / or the proof elements of that side
+    auto side = [&](auto* ftag, size_t NN, void* coms, bool proofs, const char* tag) -> int {
+      typedef std::remove_pointer_t<decltype(ftag)> F;
+      constexpr bool g2 = std::is_same<F, F2>::value;
+      const bool grp = g2 ? sh.yg : sh.xg;  // a group-valued side carries V
+      const int nv = g2 ? n : m, nc = g2 ? m : n, npf = g2 ? sh.kx : sh.ky, rc = g2 ? pm.SC : pm.RC,
+                cs = g2 ? pm.RC : pm.SC;
+      const uint32_t zp = (uint32_t)(g2 ? Z::G2 : Z::G1);
+      SidePlan sp;
+      sp.tm = proofs && grp ? pick_tm(c, fillN(c, NN), nc + 1, 1, g2, 1) : 1;
+      ComOutputs out{sp};
+      if (coms) {
+        out.add(nv, 0, 0, [&](int i, int k, ComOutputs& o) {
+          if (grp)
+            o.fix(rc + 2 * i, tb_u(0, k), rc + 2 * i + 1, tb_u(1, k), 0xFF, 0);
+          else
+            o.fix(rc + i, tb_u(0, k), 0, 0xFF, 0xFF, 0);
+        });
+        sp.ncom = nv;
+      }
+      if (proofs)
+        out.add(npf, 1, 0, [&](int l, int k, ComOutputs& o) {
+          if (!grp)  // a multiple of u0 / v0: Tf, or QuadEqu's pi'
+            return o.fix(g2 && ty == GS_QUAD ? pm.OM : pm.TC + l, tb_u(0, k), 0, 0xFF, 0xFF, 0);
+          o.fix(pm.OM, tb_u(0, k), pm.OM + 1, tb_u(1, k), 0xFF, 0);
+          if (k == 0) return;  // (O, V)
+          std::vector<VarTask> terms;
+          for (int j = 0; j < nc; j++) terms.push_back(mkvar(cs + j, 1, j, 0));
+          terms.push_back(mkvar(pm.NT, 2, 0, 0));
+          o.terms(terms);
+        });
+      const ArrTab arrs = arr_tab({{1, g2 ? B : A, (uint32_t)nc * zp, grp}, {2, tg, zp, grp}});
+      const OutTab outs = out_tab(coms, (uint32_t)nv * 2 * zp, g2 ? pi : theta, (uint32_t)npf * 2 * zp);
+      RangeGuard rg(g2 ? "gs.simulate.g2" : "gs.simulate.g1");
+      const unsigned masks[4] = {0u, proofs && grp ? BIT(g2 ? SI_B : SI_A) | BIT(SI_TG) : 0u,
+                                 coms ? BIT(g2 ? SO_YC : SO_XC) : 0u, proofs ? BIT(g2 ? SO_PI : SO_TH) : 0u};
+      const void* tab = g2 ? c->tabs->tab16_g2.p : c->tabs->tab16_g1.p;
+      return run_side<C, F>(c, tag, NN, sp, arrs, (const S*)pool, pm.total, (const Aff<F>*)tab, outs, nullptr, nullptr,
+                            nullptr, masks);
+    };
+    if (shared) {  // the Statement's commitments once (equation 0 of the pool holds Rc, Sc), then the E proofs
+      if (xcoms) RC(side((F1*)nullptr, 1, xcoms, false, ".sc1"));
+      if (ycoms) RC(side((F2*)nullptr, 1, ycoms, false, ".sc2"));
+      xcoms = ycoms = nullptr;
+    }
+    RC(side((F1*)nullptr, N, xcoms, true, ".sm1"));
+    return side((F2*)nullptr, N, ycoms, true, ".sm2");
+  }
+
   // commitments only (commit.rs:59-256): a "prove" side with no proof elements
   template <class F>
   static int commit(gs_ctx* c, size_t count, bool group, const void* vars, const void* rand, void* out,
@@ -3027,6 +3111,16 @@ static void clear_extraction_key(gs_ctx* c) {
   hipStreamSynchronize(c->stream);
 }
 
+// Forget the simulation trapdoor: the context's copy is zeroed on the stream, behind the simulations already enqueued.
+static void clear_simulation_key(gs_ctx* c) {
+  c->have_skey = false;
+  if (!c->skey.p) return;
+  hipSetDevice(c->device);
+  drain_ctx(c);
+  hipMemsetAsync(c->skey.p, 0, c->skey.cap, c->stream);
+  hipStreamSynchronize(c->stream);
+}
+
 static int check_ctx(gs_ctx* c, bool need_crs) {
   if (!c) return GS_ERR_ARG;
   hipError_t e = hipSetDevice(c->device);
@@ -3201,6 +3295,39 @@ template <class C> static int set_extraction_key_impl(gs_ctx* c, const void* key
   c->have_xkey = true;
   return GS_OK;
 }
+// ---- simulation with the hiding CRS's trapdoor (entry points below) ---------------------------------------------------
+// The two checks W1 == t1 u0 and W2 == t2 v0 (W = key[1] + (O, generator), derived at gs_set_crs), then the context's
+// copy of t1, t2.  The staged copy goes whatever happened; a refused key is wiped by the caller (clear_simulation_key).
+template <class C> static int set_simulation_key_impl(gs_ctx* c, const void* key) {
+  RC(ensure(c, c->skey, 2 * SZ_FR));
+  void* stage;
+  RC(scratch(c, "skey.in", 2 * SZ_FR + 4, &stage));
+  const Fr<C>* dk = (const Fr<C>*)stage;
+  uint8_t* dok = (uint8_t*)stage + 2 * SZ_FR;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(stage, key, 2 * SZ_FR, hipMemcpyHostToDevice));
+  int rc = launch(c, "k_sim_key.g1", k_sim_key<C, Fq<C>>, 2, 64, dk, (const uint8_t*)c->tabs->crs_g1.p, dok);
+  if (rc == GS_OK)
+    rc = launch(c, "k_sim_key.g2", k_sim_key<C, Fp2<C>>, 2, 64, dk + 1, (const uint8_t*)c->tabs->crs_g2.p, dok + 2);
+  uint8_t ok[4] = {0, 0, 0, 0};
+  hipError_t e = hipSuccess, e1 = hipSuccess;
+  if (rc == GS_OK) e = hipMemcpyAsync(ok, dok, 4, hipMemcpyDeviceToHost, c->stream);
+  if (rc == GS_OK) e1 = hipMemcpyAsync(c->skey.p, stage, 2 * SZ_FR, hipMemcpyDeviceToDevice, c->stream);
+  hipMemsetAsync(stage, 0, 2 * SZ_FR, c->stream);
+  hipError_t e2 = hipStreamSynchronize(c->stream);
+  if (rc != GS_OK) return rc;
+  if (e != hipSuccess || e1 != hipSuccess || e2 != hipSuccess)
+    return fail(c, GS_ERR_DEVICE, "gs_set_simulation_key", e != hipSuccess ? e : e1 != hipSuccess ? e1 : e2);
+  static const char* const what[4] = {
+      "gs_set_simulation_key: (u[1] + (O, g1)).0 != t1 * u[0].0 (wrong t1)",
+      "gs_set_simulation_key: (u[1] + (O, g1)).1 != t1 * u[0].1 (a binding CRS has no trapdoor, or wrong t1)",
+      "gs_set_simulation_key: (v[1] + (O, g2)).0 != t2 * v[0].0 (wrong t2)",
+      "gs_set_simulation_key: (v[1] + (O, g2)).1 != t2 * v[0].1 (a binding CRS has no trapdoor, or wrong t2)"};
+  for (int i = 0; i < 4; i++)
+    if (!ok[i]) return fail(c, GS_ERR_ARG, what[i]);
+  c->have_skey = true;
+  return GS_OK;
+}
 template <class C, class F> static int extract_impl(gs_ctx* c, const char* name, int slot, size_t n, const void* coms, void* out) {
   const SharedDigits* sd = (const SharedDigits*)c->xkey.p + slot;
   if (c->endo)
@@ -3277,6 +3404,8 @@ void gs_ctx_destroy(gs_ctx* c) {
   drain_ctx(c);
   clear_extraction_key(c);
   if (c->xkey.p) hipFree(c->xkey.p);
+  clear_simulation_key(c);
+  if (c->skey.p) hipFree(c->skey.p);
   for (auto& t : c->dlog)
     for (DevBuf* b : {&t.slots, &t.aux})
       if (b->p) hipFree(b->p);
@@ -3478,6 +3607,7 @@ int gs_set_crs(gs_ctx* c, const void* crs) {
   if (!crs) return GS_ERR_ARG;
   drain_ctx(c);  // kernels in flight read the tables this call may free (their last reference can be this context's)
   clear_extraction_key(c);  // a key belongs to the CRS it was checked against
+  clear_simulation_key(c);
   return DISPATCH(c, set_crs(c, crs));
 }
 
@@ -4042,6 +4172,70 @@ int gs_rerandomize_statement(gs_ctx* c, int ty, size_t E, int m, int n, const vo
                              void* theta_out) {
   return rerand_host(c, rerand_args(ty, E, m, n, true, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, ycoms_out,
                                     pi_out, theta_out));
+}
+
+// ---- simulate: commitments and proofs from the hiding CRS's trapdoor, without any witness ---------------------------
+static const ArrDesc kSimulateArrs[] = {
+    {SI_A, lay::A, ARR_IN},       {SI_B, lay::B, ARR_IN},       {SI_G, lay::GAMMA, ARR_IN}, {SI_TG, lay::TARGET, ARR_IN},
+    {SI_R, lay::R, ARR_IN},       {SI_S, lay::S, ARR_IN},       {SI_T, lay::T, ARR_IN},
+    {SO_XC, lay::XCOMS, ARR_OUT | ARR_OPT}, {SO_YC, lay::YCOMS, ARR_OUT | ARR_OPT}, {SO_PI, lay::PI, ARR_OUT},
+    {SO_TH, lay::THETA, ARR_OUT}};
+static const int* simulate_order(int) {
+  // staging order = the order simulate() asks for them: the scalars, then the G1 side's points, then the G2 side's
+  // (of A, B, target the scalar-valued ones are read by the preparation kernel; they are small)
+  static const int order[] = {SI_G, SI_R, SI_S, SI_T, SI_TG, SI_A, SI_B};
+  return order;
+}
+static int simulate_run(gs_ctx* c, const BatchArgs& a) {
+  const void* const* p = a.p;
+  return DISPATCH(c, simulate(c, a.ty, a.N, a.m, a.n, p[SI_A], p[SI_B], p[SI_G], p[SI_TG], p[SI_R], p[SI_S], p[SI_T],
+                              a.out(SO_XC), a.out(SO_YC), a.out(SO_PI), a.out(SO_TH), a.shared));
+}
+static const Op kSimulate = {kSimulateArrs, sizeof kSimulateArrs / sizeof *kSimulateArrs, simulate_order, 7, simulate_run};
+static int simulate_call(gs_ctx* c, const char* fn, bool host, const BatchArgs& a) {
+  if (c && c->rec) return fail(c, GS_ERR_ARG, (std::string(fn) + " inside a mixed call").c_str());
+  RC(batch_check(c, kSimulate, a));
+  if (!c->have_skey) return fail(c, GS_ERR_ARG, (std::string(fn) + ": gs_set_simulation_key has not been called").c_str());
+  if (a.ty == GS_PPE)
+    return fail(c, GS_ERR_ARG,
+                (std::string(fn) + ": GS_PPE is refused -- iota_T(t) of a general target t in GT has no preimage the "
+                                   "simulator could pair its way to, and a PPE with target one is already simulated by "
+                                   "gs_prove_batch at the identity witness").c_str());
+  if (a.N == 0) return GS_OK;
+  if (!host) return kSimulate.run(c, a);
+  // outputs do not alias inputs or each other (the staged copies would hide it; the device form's contract)
+  const lay::Layout L = layout_of(c, a);
+  for (const ArrDesc& o : kSimulateArrs) {
+    if (!(o.flags & ARR_OUT) || !a.p[o.slot]) continue;
+    for (const ArrDesc& i : kSimulateArrs) {
+      if (i.slot == o.slot || !a.p[i.slot]) continue;
+      uintptr_t x = (uintptr_t)a.p[o.slot], y = (uintptr_t)a.p[i.slot];
+      if (x < y + L.bytes[i.arr] && y < x + L.bytes[o.arr])
+        return fail(c, GS_ERR_ARG, (std::string(fn) + ": an output overlaps another array").c_str());
+    }
+  }
+  return batch_host_checked(c, kSimulate, a);
+}
+#define GS_SIMULATE_ENTRY(NAME, HOST, SHARED)                                                                        \
+  int NAME(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G, const void* target, \
+           const void* Rc, const void* Sc, const void* Tf, void* xcoms, void* ycoms, void* pi, void* theta) {         \
+    return simulate_call(c, #NAME, HOST,                                                                             \
+                         BatchArgs{ty, N, m, n, SHARED, {A, B, G, target, Rc, Sc, Tf, xcoms, ycoms, pi, theta}});     \
+  }
+GS_SIMULATE_ENTRY(gs_simulate_batch_dev, false, false)
+GS_SIMULATE_ENTRY(gs_simulate_batch, true, false)
+GS_SIMULATE_ENTRY(gs_simulate_statement_dev, false, true)
+GS_SIMULATE_ENTRY(gs_simulate_statement, true, true)
+#undef GS_SIMULATE_ENTRY
+int gs_set_simulation_key(gs_ctx* c, const void* t1t2) {
+  RC(check_ctx(c, false));
+  clear_simulation_key(c);
+  if (!t1t2) return GS_OK;
+  RC(check_ctx(c, true));
+  if (c->rec) return fail(c, GS_ERR_ARG, "gs_set_simulation_key inside a mixed call");
+  int rc = DISPATCH_FN(c, set_simulation_key_impl, (c, t1t2));
+  if (rc != GS_OK) clear_simulation_key(c);  // a refused key leaves nothing behind
+  return rc;
 }
 
 // ---- witness extraction with the binding key ---------------------------------------

@@ -263,6 +263,108 @@ __global__ void __launch_bounds__(64, GS_WPE) k_extract_key(const Fr<C>* key, co
   }
 }
 
+// ---- proof simulation with the hiding CRS's trapdoor (gs_simulate_*) ---------------------------------------------------
+// On the CRS of gs_crs_generate_hiding W = key[1] + (O, generator) = t key[0]: whoever holds t1, t2 answers every
+// equation with commitments and proofs that are fixed-base combinations of u / v, plus one short variable-base sum.
+//
+// Key-set time, lanes 0 and 1: does W.i == key * key0.i hold (pts = u0.0 u0.1 u1.0 u1.1 W.0 W.1, the CRS's device
+// copy)?  Plain double-and-add, so the answer is defined whatever the CRS holds.  key: one Montgomery Fr.
+template <class C, class F>
+__global__ void __launch_bounds__(64, GS_WPE) k_sim_key(const Fr<C>* key, const uint8_t* pts, uint8_t* ok) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= 2) return;
+  const Fr<C> k = from_mont(key[0]);
+  Aff<F> P, R;
+  aff_load<C>(P, pts + i * AFFB(C, F));
+  Jac<F> J;
+  jac_smul(J, P, k);
+  jac_to_aff(R, J);
+  BFq<C> got[AFFB(C, F) / sizeof(BFq<C>)];
+  aff_store<C>(reinterpret_cast<uint8_t*>(got), R);
+  const uint8_t *a = reinterpret_cast<const uint8_t*>(got), *b = pts + (4 + i) * AFFB(C, F);
+  bool same = true;
+  for (size_t j = 0; j < AFFB(C, F); j++) same = same && a[j] == b[j];
+  ok[i] = same ? 1 : 0;
+}
+
+// one Fr that every lane of the launch reads alike (the trapdoor): through the constant address space, i.e. scalar
+// loads into scalar registers, not one vector load per lane
+template <class C> __device__ __forceinline__ Fr<C> ld_uniform_fr(const Fr<C>* p) {
+  typedef const __attribute__((address_space(4))) uint32_t* cptr;
+  cptr w = (cptr) reinterpret_cast<const uint32_t*>(p);
+  Fr<C> r;
+#pragma unroll
+  for (int i = 0; i < FrM<C>::N; i++) r.v[i] = w[i];
+  return r;
+}
+
+// The simulator's scalars, one lane per equation (all types but PPE).  Inputs in the layouts of gs_prove_batch's R, S, T:
+// Rc[m][kx], Sc[n][ky] (coordinates of the commitments in the bases u / v), Tf[ky][kx] (the free proof scalars); as / bs /
+// tq: the scalar constants and target where the type has them; key = t1, t2 (Montgomery).  The pool receives, canonical:
+//   RC, SC   Rc, Sc: the fixed-base scalars of the commitments, and the Straus scalars of V (Sc_j for MSMEG1, Rc_i for MSMEG2)
+//   TC       Tf: the fixed-base scalars of the proof elements that are multiples of u0 / v0 alone
+//   OM       MSMEG1: sum_i e_i Rc_ia - Tf[0][a], e_i = t2 b_i + sum_j Gamma_ij Sc_j   (theta's coordinates on u0, u1)
+//            MSMEG2: sum_j f_j Sc_jl - Tf[l][0], f_j = t1 a_j + sum_i Rc_i Gamma_ij   (pi's coordinates on v0, v1)
+//            QuadEqu: t2 sum_i Rc_i b_i + t1 sum_j a_j Sc_j + sum_ij Rc_i Gamma_ij Sc_j - t t1 t2 - Tf[0][0]   (pi = OM v0)
+//   NT       -t2 (MSMEG1) / -t1 (MSMEG2): the Straus scalar of the target in V
+// shared_vars: a Statement -- ONE copy of Rc, Sc for all equations.
+template <class C>
+struct k_prep_sim {
+  static __device__ __forceinline__ void run(size_t e, size_t N, int ty, int m, int n, const Fr<C>* G, const Fr<C>* as,
+                                            const Fr<C>* bs, const Fr<C>* tq, const Fr<C>* R, const Fr<C>* S,
+                                            const Fr<C>* T, const Fr<C>* key, PoolMap pm, Fr<C>* pool, int shared_vars) {
+  if (e >= N) return;
+  typedef Fr<C> S_;
+  const int kx = (ty == 1) ? 2 : 1, ky = (ty == 2) ? 2 : 1;
+  const size_t ev = shared_vars ? 0 : e;
+  G += e * m * n;
+  R += ev * m * kx;
+  S += ev * n * ky;
+  T += e * ky * kx;
+  const S_ t1 = ld_uniform_fr<C>(key), t2 = ld_uniform_fr<C>(key + 1);
+  S_* P = pool + e * pm.total;
+  for (int i = 0; i < m * kx; i++) P[pm.RC + i] = from_mont(R[i]);
+  for (int i = 0; i < n * ky; i++) P[pm.SC + i] = from_mont(S[i]);
+  for (int i = 0; i < ky * kx; i++) P[pm.TC + i] = from_mont(T[i]);
+  S_ c0 = fzero<FrM<C>>(), c1 = fzero<FrM<C>>();
+  if (ty == 1) {
+    bs += e * m;
+    for (int i = 0; i < m; i++) {
+      S_ ei = mul(t2, bs[i]);
+      for (int j = 0; j < n; j++) ei = add(ei, mul(G[i * n + j], S[j]));
+      c0 = add(c0, mul(ei, R[2 * i]));
+      c1 = add(c1, mul(ei, R[2 * i + 1]));
+    }
+    P[pm.OM] = from_mont(sub(c0, T[0]));
+    P[pm.OM + 1] = from_mont(sub(c1, T[1]));
+    P[pm.NT] = from_mont(neg(t2));
+  } else if (ty == 2) {
+    as += e * n;
+    for (int j = 0; j < n; j++) {
+      S_ fj = mul(t1, as[j]);
+      for (int i = 0; i < m; i++) fj = add(fj, mul(R[i], G[i * n + j]));
+      c0 = add(c0, mul(fj, S[2 * j]));
+      c1 = add(c1, mul(fj, S[2 * j + 1]));
+    }
+    P[pm.OM] = from_mont(sub(c0, T[0]));
+    P[pm.OM + 1] = from_mont(sub(c1, T[1]));
+    P[pm.NT] = from_mont(neg(t1));
+  } else {
+    as += e * n;
+    bs += e * m;
+    for (int i = 0; i < m; i++) {
+      S_ ei = mul(t2, bs[i]);
+      for (int j = 0; j < n; j++) ei = add(ei, mul(G[i * n + j], S[j]));
+      c0 = add(c0, mul(ei, R[i]));
+    }
+    for (int j = 0; j < n; j++) c1 = add(c1, mul(as[j], S[j]));
+    c0 = add(c0, mul(t1, c1));
+    c0 = sub(c0, mul(tq[e], mul(t1, t2)));
+    P[pm.OM] = from_mont(sub(c0, T[0]));
+  }
+}
+};
+
 // ---- bounded discrete logarithms (gs_dlog_*, gs_extract_scalar_*) ------------------------------------------------------
 // Baby-step giant-step for x in [0, 2^bits) with x G = P.  B = 2^log2_table baby steps j G,
 // j = 1..B, are kept by the x coordinate alone (one entry serves +j and -j) in an open-addressing table of 2 B slots of

@@ -13,6 +13,8 @@ top of the C ABI (same names, argument meaning and error behaviour):
     rerandomize(equ, com_proof, crs, rng) -> CProof                      (new) fresh commitments and proof, no witness
     generate_crs_with_key -> (CRS, key), extract(commit, crs, key)        (new) open commitments with the binding key
     extract_scalars(commit, crs, key, bits, log2_table=None)              (new) committed scalars < 2^bits back themselves
+    generate_crs_with_trapdoor -> (hiding CRS, trapdoor), <Equation>.simulate(crs, trapdoor, rng), Statement.simulate,
+    equivocate(x, r, x_new, t)                                            (new) proofs without a witness, hiding CRS
     EquProof {pi, theta, equ_type, rand}, CProof {xcoms, ycoms, equ_proofs} prove.rs:55-69
 
 Values are numpy uint64 limb arrays in the boundary layout of include/gs_amd.h
@@ -70,6 +72,23 @@ def generate_crs_with_key(p1, p2, rng, curve=0, device=0, hiding=False):
     made under this CRS (extract below): keep it secret, or drop it."""
     sc = np.concatenate([rng.fr() for _ in range(4)])
     return _crs_from_scalars(p1, p2, sc, curve, device, hiding), sc[:8].copy()
+
+
+def generate_crs_with_trapdoor(p1, p2, rng, curve=0, device=0):
+    """The HIDING CRS (generator.rs:65-77) together with its simulation trapdoor: (CRS, trapdoor), trapdoor = t1 || t2
+    (8 u64 limbs, Montgomery form).  The draws are those of generate_crs, so the same rng state gives the same CRS as
+    generate_crs(.., hiding=True).  The trapdoor answers every equation without a witness (equ.simulate below) and opens
+    a scalar commitment to any value (equivocate): keep it secret, or drop it."""
+    sc = np.concatenate([rng.fr() for _ in range(4)])
+    return _crs_from_scalars(p1, p2, sc, curve, device, True), sc[8:16].copy()
+
+
+def equivocate(x, r, x_new, t, curve=0):
+    """The randomness that opens the hiding scalar commitment c = x W + r key0 (commit_scalar_to_B1 / _B2 under a CRS of
+    generate_crs_with_trapdoor) to x_new instead: r + (x - x_new) t, since W = t key0 there.  t is the trapdoor scalar of
+    the commitment's side (t1 for B1, t2 for B2).  All values are Montgomery Fr limbs; host Fr arithmetic, no GPU."""
+    q = _FR_ORDER[curve]
+    return _fr_limbs((_fr_int(r, q) + (_fr_int(x, q) - _fr_int(x_new, q)) * _fr_int(t, q)) % q, q)
 
 
 def extract(commit, crs, key):
@@ -273,6 +292,16 @@ class _Equation:
         assert len(pi) == kx and len(theta) == ky
         return EquProof(pi, theta, self.TYPE, T)
 
+    # -- simulation (the hiding CRS's trapdoor; no witness) -------------------
+    def simulate(self, crs, trapdoor, rng):
+        """A CProof for this equation WITHOUT a witness (gs_simulate_batch), from the trapdoor of
+        generate_crs_with_trapdoor: it verifies whatever the constants and the target are, and is distributed like an
+        honest proof under that CRS.  Draws Rc (m x kx), then Sc (n x ky), then Tf (ky x kx) from `rng`; the commitments
+        carry Rc / Sc as their `rand` (coordinates in the CRS basis: they open nothing), the proof carries Tf.  Refused
+        for PPE (GsError code 3); raises GsError when `trapdoor` is not that of `crs`, in particular on a binding CRS.
+        The trapdoor stays installed in crs.engine until crs.engine.set_simulation_key(None)."""
+        return Statement([self]).simulate(crs, trapdoor, rng)
+
     # -- Verifiable --------------------------------------------------------
     def verify(self, com_proof, crs):  # verifier.rs:23-157
         assert len(com_proof.equ_proofs) == 1
@@ -469,6 +498,29 @@ class Statement:
         pis, ths = _split(out["pi"], E * kx), _split(out["theta"], E * ky)
         proofs = [EquProof(pis[e * kx:(e + 1) * kx], ths[e * ky:(e + 1) * ky], self.TYPE, Ts[e]) for e in range(E)]
         return CProof(xcoms, ycoms, proofs)
+
+    def simulate(self, crs, trapdoor, rng):
+        """A CProof for the whole statement WITHOUT a witness (gs_simulate_statement): one simulated commitment set,
+        one proof per equation.  Draw order: Rc, Sc, then Tf of equation 0, 1, ..  Refused for PPE."""
+        kx, ky = self._kxky()
+        E = len(self.equations)
+        m, n = len(self.equations[0].b_consts), len(self.equations[0].a_consts)
+        assert m >= 1 and n >= 1
+        for equ in self.equations:
+            equ._check_statement_shape(m, n)
+        crs.engine.set_simulation_key(trapdoor)
+        Rc = [[rng.fr() for _ in range(kx)] for _ in range(m)]
+        Sc = [[rng.fr() for _ in range(ky)] for _ in range(n)]
+        Ts = [[[rng.fr() for _ in range(kx)] for _ in range(ky)] for _ in range(E)]
+        cat = np.concatenate
+        out = crs.engine.simulate_statement(
+            self.TYPE, E, m, n, cat([_cat(e.a_consts, 0) for e in self.equations]),
+            cat([_cat(e.b_consts, 0) for e in self.equations]), cat([_flat_mat(e.gamma) for e in self.equations]),
+            cat([np.asarray(e.target, dtype=np.uint64).reshape(-1) for e in self.equations]), _flat_mat(Rc),
+            _flat_mat(Sc), cat([_flat_mat(T) for T in Ts]))
+        pis, ths = _split(out["pi"], E * kx), _split(out["theta"], E * ky)
+        proofs = [EquProof(pis[e * kx:(e + 1) * kx], ths[e * ky:(e + 1) * ky], self.TYPE, Ts[e]) for e in range(E)]
+        return CProof(Commit1(_split(out["xcoms"], m), Rc), Commit2(_split(out["ycoms"], n), Sc), proofs)
 
     def _witness_arrays(self, xvars, yvars):
         """(m, n, X, Y, A, B, Gamma as gs_eval_statement takes them) after the shape checks"""

@@ -12,6 +12,8 @@
  *   gs_verify_batch_rlc_locate <- (new) the same check with the product tree kept and descended: which proofs are bad
  *   gs_rerandomize_batch   <- (new) rerandomization of commitments and proofs without the witness (the same
  *                             algebra as src/prover/prove.rs:92-171,195-274,298-379,409-488 applied to fresh randomness)
+ *   gs_simulate_batch      <- (new) commitments and proofs WITHOUT a witness from the trapdoor of the hiding CRS, the
+ *                             simulation key that src/generator.rs:65-77 prepares and nothing in the reference uses
  *   gs_eval_batch / gs_check_witness_batch <- (new) the left-hand sides of src/statement.rs:17-21 at a witness: an
  *                             equation's target, and whether a witness satisfies it (tests/prover.rs:50-52,87-90,125-128,
  *                             160-162 write the same sums by hand with arkworks)
@@ -319,6 +321,76 @@ int gs_extract_g1_dev(gs_ctx*, size_t count, const void* coms_com1, void* out_g1
 int gs_extract_g2_dev(gs_ctx*, size_t count, const void* coms_com2, void* out_g2);
 int gs_extract_g1(gs_ctx*, size_t count, const void* coms_com1, void* out_g1);
 int gs_extract_g2(gs_ctx*, size_t count, const void* coms_com2, void* out_g2);
+
+/* ---- simulate (the hiding key's trapdoor answers equations without a witness) ---------------------------------------
+ * The CRS of gs_crs_generate_hiding is u0 = (p1, a1 p1), u1 = t1 u0 - (O, p1) (and v with a2, t2, p2), so that
+ *   W1 = u1 + (O, g1) = t1 u0        W2 = v1 + (O, g2) = t2 v0.
+ * Whoever drew t1, t2 can produce commitments and proofs for an equation WITHOUT ANY WITNESS -- also for an equation no
+ * witness satisfies -- and they are distributed exactly like honest ones (perfect zero-knowledge).  That is the simulator
+ * of the security experiments of credentials, ballots and shuffles, and a way to load a verifier pipeline without real
+ * witnesses.  On the binding key (gs_crs_generate) W1 != t1 u0 and nothing can be simulated; that key is refused.
+ *
+ * gs_set_simulation_key: t1t2_fr2 is a HOST pointer to t1, t2 (two Fr, Montgomery limbs); NULL forgets the key.  Needs an
+ * installed CRS (GS_ERR_NOCRS) and checks u[1] + (O, g1) == t1 u[0] and v[1] + (O, g2) == t2 v[0], component by component,
+ * on the device with plain double-and-add (the verdict is defined whatever the CRS holds): a binding CRS or a wrong key
+ * returns GS_ERR_ARG, gs_last_error names the check that failed, and no key is installed (an earlier one is gone too).
+ * The call synchronises the stream.  gs_set_crs forgets the key (also when the same CRS comes back).  The key is a
+ * SECRET, handled as gs_set_extraction_key handles its own: the context's copy and the staged copy are zeroed on the
+ * stream when the key is cleared, replaced or refused, on gs_set_crs and on gs_ctx_destroy; the simulator's scalar pool
+ * (it holds -t2, t2 b_i + ... and the like) is zeroed on the stream after the last kernel of every call that reads it.
+ * The caller's own buffer is the caller's to wipe.
+ *
+ * gs_simulate_batch: N equations of one type and shape, A, B, Gamma, target as gs_verify_batch takes them, and
+ *   Rc[N][m][kx]   the coordinates of the x-commitments in the basis u     (layout of gs_prove_batch's R)
+ *   Sc[N][n][ky]   the same for y in the basis v                           (layout of S)
+ *   Tf[N][ky][kx]  the free proof scalars                                  (layout of T)
+ * all UNIFORM, FRESH and SECRET: randomness is an input here as everywhere.  Outputs (xcoms / ycoms may be NULL):
+ *   c_i = sum_a Rc_ia u_a          d_j = sum_b Sc_jb v_b      byte for byte what gs_prove_batch writes for the all-identity
+ *                                                             (all-zero) witness with R = Rc, S = Sc
+ *   GS_QUAD    theta = Tf[0][0] u0,  pi = pi' v0 with
+ *              pi' = t2 sum_i Rc_i b_i + t1 sum_j a_j Sc_j + sum_ij Rc_i Gamma_ij Sc_j - t t1 t2 - Tf[0][0]
+ *   GS_MSMEG1  pi_k = Tf[0][k] v0,  theta = (O, V) + (sum_i e_i Rc_i0 - Tf[0][0]) u0 + (sum_i e_i Rc_i1 - Tf[0][1]) u1
+ *              with e_i = t2 b_i + sum_j Gamma_ij Sc_j and V = sum_j Sc_j A_j - t2 T
+ *   GS_MSMEG2  theta_l = Tf[l][0] u0,  pi = (O, V) + (sum_j f_j Sc_j0 - Tf[0][0]) v0 + (sum_j f_j Sc_j1 - Tf[1][0]) v1
+ *              with f_j = t1 a_j + sum_i Rc_i Gamma_ij and V = sum_i Rc_i B_i - t1 T
+ *   GS_PPE     REFUSED (GS_ERR_ARG): iota_T(t) of a general target t in GT has no preimage the simulator could pair its
+ *              way to, and a PPE with target one is already simulated by gs_prove_batch at the identity witness.
+ * gs_verify_batch accepts the output under the hiding CRS for ANY A, B, Gamma, target.  For a satisfied equation the
+ * honest proof under the hiding CRS equals the simulated one at the corresponding coordinates -- a G1 variable
+ * X_i = xi_i g1 committed with R_i sits at Rc_i = (R_i0 + xi_i t1, R_i1 - xi_i), a scalar x_i at Rc_i = R_i + x_i t1
+ * (likewise Sc with t2), Tf = the v0- (u0-) coordinates of the honest pi_k (theta_l) -- BYTE FOR BYTE.
+ * gs_simulate_statement: E equations over ONE set of commitments: Rc[m][kx], Sc[n][ky], xcoms[m], ycoms[n] are one copy,
+ * written once; A, B, Gamma, target, Tf[E][ky][kx], pi and theta are per equation; gs_verify_statement accepts.
+ * Errors: GS_ERR_ARG while no key is installed, for GS_PPE, and inside a mixed call; the host forms return GS_ERR_ARG when
+ * an output overlaps an input or another output (for the _dev forms that is the caller's contract); shapes and the
+ * remaining errors are those of gs_prove_batch; N == 0 is a no-op.  The _dev forms only enqueue on the context's stream.
+ * The multi-GPU handles (gs_multi_*) have NO counterpart: use a shard's context (gs_multi_ctx).  A and B come from the
+ * equation; as on the other compute entry points nothing is checked and points outside the prime-order subgroups give
+ * undefined results unless "endo" = 0, under which the variable-base lanes run plain ("k_var.plain").  "var_tm",
+ * "var_w", "var_w2", "var_ws_lanes" and "red_k" act as they do elsewhere.
+ * How it is computed: one lane of Fr arithmetic per equation ("k_prep_sim"; the trapdoor is read through
+ * scalar loads), every output component one fixed-base lane on the CRS tables ("k_fix.sm1|.sm2"), V as n + 1 (m + 1)
+ * Straus terms ("k_var*.sm1|.sm2"), then the usual reductions ("k_red.sm1|.sm2"; a Statement's commitments: ".sc1|.sc2").
+ * WHEN TO CALL IT: the simulator does no more group work than gs_prove_batch with commitments on the same shape (the same
+ * commitment lanes with fewer terms, n + 1 or m + 1 Straus terms against m + n), so wherever a test bench or a trapdoor
+ * setup would otherwise invent witnesses and prove, it may simulate instead.  Measured (tools/sim_rate.py,
+ * profiles/simulate/rate.json, DESIGN.md 6.9: BLS12-381, 4 x 4, one MI355X, device-resident, median of 7, the two entries
+ * alternating), ms per call, this entry against gs_prove_batch_dev on the same shape -- MSMEG1: 2.90 against 3.53 at
+ * N = 2^12 (ratio 0.82), 14.96 against 23.15 at 2^16 (0.65); QuadEqu: 0.94 against 1.54 (0.61) and 7.05 against 13.08
+ * (0.54); MSMEG2 at 2^16: 25.16 against 35.39 (0.71). */
+int gs_set_simulation_key(gs_ctx*, const void* t1t2_fr2);
+int gs_simulate_batch_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B, const void* Gamma,
+                          const void* target, const void* Rc, const void* Sc, const void* Tf, void* xcoms, void* ycoms,
+                          void* pi, void* theta);
+int gs_simulate_batch(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B, const void* Gamma,
+                      const void* target, const void* Rc, const void* Sc, const void* Tf, void* xcoms, void* ycoms,
+                      void* pi, void* theta);
+int gs_simulate_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B,
+                              const void* Gamma, const void* target, const void* Rc, const void* Sc, const void* Tf,
+                              void* xcoms, void* ycoms, void* pi, void* theta);
+int gs_simulate_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B, const void* Gamma,
+                          const void* target, const void* Rc, const void* Sc, const void* Tf, void* xcoms, void* ycoms,
+                          void* pi, void* theta);
 
 /* ---- dlog (bounded scalar witnesses back from their images) --------------- */
 /* gs_extract_* opens a committed SCALAR to its image x * generator.  The scalars committed under Groth-Sahai (amounts,

@@ -15,6 +15,8 @@
 //   EquProof {pi, theta, equ_type, rand}, CProof  src/prover/prove.rs:55-69
 //   CRS::generate_crs_with_key, CRS::set_extraction_key, CRS::extract   (new) open commitments with the binding key
 //   CRS::dlog_prepare, CRS::extract_scalars                             (new) committed scalars < 2^bits back themselves
+//   CRS::generate_hiding_with_trapdoor, CRS::set_simulation_key, Equation::simulate, Statement::simulate
+//                                                                       (new) proofs without a witness, hiding CRS
 //
 // Values are byte strings in the boundary layout of gs_amd.h (arkworks' Montgomery
 // limbs).  `Rng` is any type with `Fr fr()`; draws happen in the reference's order
@@ -108,6 +110,11 @@ struct ExtractionKey {
   Fr a1, a2;
 };
 
+// (new) the trapdoor of a hiding CRS: W1 = t1 u0, W2 = t2 v0 (CRS::generate_hiding_with_trapdoor, Equation::simulate)
+struct SimulationKey {
+  Fr t1, t2;
+};
+
 struct CRS {  // generator.rs:35-42
   std::vector<Com1> u;
   std::vector<Com2> v;
@@ -156,6 +163,27 @@ struct CRS {  // generator.rs:35-42
     ctx->chk(rc);
   }
   void clear_extraction_key() const { ctx->chk(gs_set_extraction_key(ctx->c, nullptr)); }
+  // (new) The HIDING CRS of generator.rs:65-77 (dead code there) with its simulation trapdoor t1, t2: the draws of
+  // generate_crs.  Whoever holds the trapdoor answers every equation without a witness (Equation::simulate): keep it
+  // secret, or drop it.
+  template <class Rng>
+  static std::pair<CRS, SimulationKey> generate_hiding_with_trapdoor(const G1Affine& p1, const G2Affine& p2, Rng& rng,
+                                                                     int curve = GS_CURVE_BLS12_381, int device = 0) {
+    Bytes sc = draw_scalars(rng);
+    SimulationKey key{Fr{Bytes(sc.begin() + 64, sc.begin() + 96)}, Fr{Bytes(sc.begin() + 96, sc.begin() + 128)}};
+    return {from_scalars(p1, p2, sc, curve, device, true), key};
+  }
+  // (new) Install the trapdoor in this CRS's context (gs_set_simulation_key).  Throws std::runtime_error when it is not
+  // the trapdoor of this CRS -- in particular on a binding CRS, which has none -- and installs nothing then.
+  void set_simulation_key(const SimulationKey& key) const {
+    if (key.t1.v.size() != 32 || key.t2.v.size() != 32) throw Panic("assertion failed: Fr is 32 bytes");
+    Bytes k = key.t1.v;
+    k.insert(k.end(), key.t2.v.begin(), key.t2.v.end());
+    int rc = gs_set_simulation_key(ctx->c, k.data());
+    for (uint8_t& b : k) *(volatile uint8_t*)&b = 0;
+    ctx->chk(rc);
+  }
+  void clear_simulation_key() const { ctx->chk(gs_set_simulation_key(ctx->c, nullptr)); }
   // (new) What the commitments bind, opened with the installed key: c.1 - a c.0 (gs_extract_g1 / gs_extract_g2).  A
   // committed group element comes back itself, a committed scalar x as x * generator (its image; x itself is a
   // discrete logarithm away).  Commitments from another party: validate them first, or run with "endo" 0 (gs_amd.h).
@@ -190,11 +218,12 @@ struct CRS {  // generator.rs:35-42
     }
     return sc;
   }
-  static CRS from_scalars(const G1Affine& p1, const G2Affine& p2, const Bytes& sc, int curve, int device) {
+  static CRS from_scalars(const G1Affine& p1, const G2Affine& p2, const Bytes& sc, int curve, int device,
+                          bool hiding = false) {
     Ctx tmp(curve, device);
     assert_eq(sc.size(), 4 * 32, "four scalars");
     Bytes raw(tmp.sz[5]);
-    tmp.chk(gs_crs_generate(tmp.c, p1.v.data(), p2.v.data(), sc.data(), raw.data()));
+    tmp.chk((hiding ? gs_crs_generate_hiding : gs_crs_generate)(tmp.c, p1.v.data(), p2.v.data(), sc.data(), raw.data()));
     size_t g1 = tmp.sz[2], g2 = tmp.sz[3], o = 0;
     auto take = [&](size_t n) {
       Bytes b(raw.begin() + o, raw.begin() + o + n);
@@ -551,6 +580,31 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     return out;
   }
 
+  // (new) A CProof for this equation WITHOUT a witness (gs_simulate_batch), from the trapdoor installed with
+  // crs.set_simulation_key: it verifies whatever the constants and the target are, and is distributed like an honest
+  // proof under the hiding CRS.  Draws Rc (m x KX), then Sc (n x KY), then Tf (KY x KX); the commitments carry Rc / Sc as
+  // their rand (coordinates in the CRS basis: they open nothing), the proof carries Tf.  PairingProduct is refused
+  // (std::runtime_error: gs_amd.h says why), as is a context without the trapdoor.
+  template <class Rng> CProof simulate(const CRS& crs, Rng& rng) const {
+    const size_t m = b_consts.size(), n = a_consts.size();
+    if (m == 0 || n == 0) throw Panic("index out of bounds: empty variable list");
+    check_statement_shape(m, n);
+    const Ctx& cx = *crs.ctx;
+    const size_t sx = is_scalar<A1>::value ? cx.sz[1] : cx.sz[2], sy = is_scalar<A2>::value ? cx.sz[1] : cx.sz[3];
+    assert_eq(target.v.size(), target_size(cx), "target size");
+    Matrix<Fr> Rc = detail::draw(rng, m, KX), Sc = detail::draw(rng, n, KY), Tf = detail::draw(rng, KY, KX);
+    Bytes A = cat(a_consts), B = cat(b_consts), G = cat(gamma), R = cat(Rc), S = cat(Sc), T = cat(Tf);
+    assert_eq(A.size(), n * sx, "a_consts bytes");
+    assert_eq(B.size(), m * sy, "b_consts bytes");
+    assert_eq(G.size(), m * n * cx.sz[1], "gamma bytes");
+    Bytes xo(m * 2 * cx.sz[2]), yo(n * 2 * cx.sz[3]), po(KX * 2 * cx.sz[3]), to(KY * 2 * cx.sz[2]);
+    cx.chk(gs_simulate_batch(cx.c, (int)TYPE, 1, (int)m, (int)n, A.data(), B.data(), G.data(), target.v.data(), R.data(),
+                             S.data(), T.data(), xo.data(), yo.data(), po.data(), to.data()));
+    CProof out{{split<Com1>(xo, m), Rc}, {split<Com2>(yo, n), Sc}, {}};
+    out.equ_proofs.push_back(EquProof{split<Com2>(po, KX), split<Com1>(to, KY), TYPE, Tf});
+    return out;
+  }
+
   // (new) ONE verdict for N CProofs of THIS equation (N showings of a credential, N ballots: what rerandomize produces)
   // from gs_verify_equation_rlc: the constants cross the ABI once, the random linear combination is taken across the
   // proofs before pairing.  rho is drawn from `rng`, which must be a CSPRNG (the rho contract of gs_amd.h); a batch with
@@ -734,6 +788,71 @@ class Statement {
         out.equ_proofs[p.idx[e]] = EquProof{{pis.begin() + e * kx, pis.begin() + (e + 1) * kx},
                                             {ths.begin() + e * ky, ths.begin() + (e + 1) * ky}, p.ty, Ts[p.idx[e]]};
     }
+    return out;
+  }
+
+  // (new) A StatementProof WITHOUT a witness (gs_simulate_statement, one call per equation type), from the trapdoor
+  // installed with crs.set_simulation_key.  The sizes of the four variable groups are those the equations imply (an
+  // MSMEG1's b_consts count the G1 variables, its a_consts the B2 scalars, ...; a group no equation uses stays empty).
+  // Draw order: the coordinates of the commitments of xg, yg, xs, ys, then Tf of equation 0, 1, ...  A statement with a
+  // PairingProduct equation is refused.
+  template <class Rng> StatementProof simulate(const CRS& crs, Rng& rng) const {
+    size_t cnt[4] = {0, 0, 0, 0};  // xg, yg, xs, ys
+    bool seen[4] = {false, false, false, false};
+    for (const Item& it : items) {
+      const int gx = xgroup(it.ty) ? 0 : 2, gy = ygroup(it.ty) ? 1 : 3;
+      if (seen[gx]) assert_eq(it.nb, cnt[gx], "b_consts.len() == xvars.len()");
+      if (seen[gy]) assert_eq(it.na, cnt[gy], "a_consts.len() == yvars.len()");
+      cnt[gx] = it.nb;
+      cnt[gy] = it.na;
+      seen[gx] = seen[gy] = true;
+    }
+    const Ctx& cx = *crs.ctx;
+    StatementProof out;
+    out.com_xg.rand = detail::draw(rng, cnt[0], 2);
+    out.com_yg.rand = detail::draw(rng, cnt[1], 2);
+    out.com_xs.rand = detail::draw(rng, cnt[2], 1);
+    out.com_ys.rand = detail::draw(rng, cnt[3], 1);
+    std::vector<Matrix<Fr>> Ts;
+    for (const Item& it : items) Ts.push_back(detail::draw(rng, ygroup(it.ty) ? 2 : 1, xgroup(it.ty) ? 2 : 1));
+    Bytes Rg = cat(out.com_xg.rand), Sg = cat(out.com_yg.rand), Rs = cat(out.com_xs.rand), Ss = cat(out.com_ys.rand);
+    Bytes cxg(cnt[0] * 2 * cx.sz[2]), cyg(cnt[1] * 2 * cx.sz[3]), cxs(cnt[2] * 2 * cx.sz[2]), cys(cnt[3] * 2 * cx.sz[3]);
+    out.equ_proofs.resize(items.size());
+    for (Part& p : parts()) {
+      const bool xg = xgroup(p.ty), yg = ygroup(p.ty);
+      const size_t m = cnt[xg ? 0 : 2], n = cnt[yg ? 1 : 3], kx = xg ? 2 : 1, ky = yg ? 2 : 1;
+      if (m == 0 || n == 0) throw Panic("index out of bounds: empty variable list");
+      const size_t tsz = p.ty == EquType::PairingProduct ? cx.sz[4] : p.ty == EquType::MultiScalarG1 ? cx.sz[2]
+                         : p.ty == EquType::MultiScalarG2 ? cx.sz[3] : cx.sz[1];
+      auto app = [](Bytes& d, const Bytes& s) { d.insert(d.end(), s.begin(), s.end()); };
+      for (size_t i : p.idx) {
+        check(items[i], m, n);
+        assert_eq(items[i].target.size(), tsz, "target size");
+        app(p.A, items[i].A);
+        app(p.B, items[i].B);
+        app(p.G, items[i].G);
+        app(p.target, items[i].target);
+        app(p.T, cat(Ts[i]));
+      }
+      const size_t E = p.idx.size(), sx = xg ? cx.sz[2] : cx.sz[1], sy = yg ? cx.sz[3] : cx.sz[1];
+      assert_eq(p.A.size(), E * n * sx, "a_consts bytes");
+      assert_eq(p.B.size(), E * m * sy, "b_consts bytes");
+      assert_eq(p.G.size(), E * m * n * cx.sz[1], "gamma bytes");
+      p.pi.assign(E * kx * 2 * cx.sz[3], 0);
+      p.theta.assign(E * ky * 2 * cx.sz[2], 0);
+      cx.chk(gs_simulate_statement(cx.c, (int)p.ty, E, (int)m, (int)n, p.A.data(), p.B.data(), p.G.data(),
+                                   p.target.data(), (xg ? Rg : Rs).data(), (yg ? Sg : Ss).data(), p.T.data(),
+                                   (xg ? cxg : cxs).data(), (yg ? cyg : cys).data(), p.pi.data(), p.theta.data()));
+      auto pis = split<Com2>(p.pi, E * kx);
+      auto ths = split<Com1>(p.theta, E * ky);
+      for (size_t e = 0; e < E; e++)
+        out.equ_proofs[p.idx[e]] = EquProof{{pis.begin() + e * kx, pis.begin() + (e + 1) * kx},
+                                            {ths.begin() + e * ky, ths.begin() + (e + 1) * ky}, p.ty, Ts[p.idx[e]]};
+    }
+    out.com_xg.coms = split<Com1>(cxg, cnt[0]);
+    out.com_yg.coms = split<Com2>(cyg, cnt[1]);
+    out.com_xs.coms = split<Com1>(cxs, cnt[2]);
+    out.com_ys.coms = split<Com2>(cys, cnt[3]);
     return out;
   }
 
