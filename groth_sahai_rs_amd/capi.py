@@ -47,7 +47,21 @@ SYMBOLS = [
     "gs_check_witness_statement",
     "gs_set_simulation_key", "gs_simulate_batch_dev", "gs_simulate_batch", "gs_simulate_statement_dev",
     "gs_simulate_statement",
+    "gs_rand_set_key", "gs_rand_fr_dev", "gs_rand_fr", "gs_rand_rho_dev", "gs_rand_rho",
+    "gs_prove_batch_drawn_dev", "gs_prove_batch_drawn", "gs_prove_statement_drawn_dev", "gs_prove_statement_drawn",
+    "gs_rerandomize_batch_drawn_dev", "gs_rerandomize_batch_drawn", "gs_rerandomize_statement_drawn_dev",
+    "gs_rerandomize_statement_drawn",
 ]
+# the generator's nonce domains (include/gs_amd.h: GS_RAND_*); callers' own draws use domains >= GS_RAND_USER
+GS_RAND_PROVE_R, GS_RAND_PROVE_S, GS_RAND_PROVE_T = 0x0101, 0x0102, 0x0103
+GS_RAND_RERAND_R, GS_RAND_RERAND_S, GS_RAND_RERAND_T = 0x0201, 0x0202, 0x0203
+GS_RAND_RHO = 0x0301
+GS_RAND_USER = 0x10000
+_HEAD_ARGTYPES = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int]
+# (..., X, Y, A, B, Gamma, uint64 stream, R_out, S_out, T_out, xcoms, ycoms, pi, theta)
+_PROVE_DRAWN_ARGTYPES = _HEAD_ARGTYPES + [ctypes.c_void_p] * 5 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7
+# (..., A, B, Gamma, xcoms, ycoms, pi, theta, uint64 stream, R_out, S_out, T_out, the four outputs)
+_RERAND_DRAWN_ARGTYPES = _HEAD_ARGTYPES + [ctypes.c_void_p] * 7 + [ctypes.c_uint64] + [ctypes.c_void_p] * 7
 # (gs_ctx*, int equ_type, size_t N, int m, int n, X, Y, A, B, Gamma, ...): gs_eval_* end in target_out, gs_check_witness_*
 # in target, ok
 _EVAL_ARGTYPES = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 6
@@ -111,6 +125,18 @@ def load_library():
                 # (hasattr: GS_AMD_LIB may name an older build for an A/B run of the entries it does have; calling an
                 # entry it lacks still fails loudly, with ctypes' AttributeError)
                 getattr(_LIB, n).argtypes = _EVAL_ARGTYPES if n.startswith("gs_eval_") else _CHECK_ARGTYPES
+            elif (n.startswith("gs_rand_") or n.endswith(("_drawn", "_drawn_dev"))) and hasattr(_LIB, n):
+                # 64-bit stream numbers and offsets: ctypes would pass a bare Python int as a C int
+                f = getattr(_LIB, n)
+                if n == "gs_rand_set_key":
+                    f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+                elif n.startswith("gs_rand_fr"):
+                    f.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t,
+                                  ctypes.c_void_p]
+                elif n.startswith("gs_rand_rho"):
+                    f.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_size_t, ctypes.c_void_p]
+                else:
+                    f.argtypes = _PROVE_DRAWN_ARGTYPES if n.startswith("gs_prove_") else _RERAND_DRAWN_ARGTYPES
     return _LIB
 
 
@@ -410,6 +436,152 @@ class Engine:
     def simulate_statement_dev(self, ty, E, m, n, A, B, Gamma, target, Rc, Sc, Tf, xcoms, ycoms, pi, theta):
         self._simulate("gs_simulate_statement_dev", ty, E, m, n, A, B, Gamma, target, Rc, Sc, Tf,
                        (xcoms, ycoms, pi, theta))
+
+    # -- randomness drawn on the device (keyed, counter-addressed ChaCha20) ------------------------------------------
+    def rand_set_key(self, key):
+        """Install the generator's 32-byte key (gs_rand_set_key); None forgets it.  The key comes from a CSPRNG, and a
+        (key, stream) pair serves ONE call of one operation."""
+        if key is None:
+            self._chk(self.lib.gs_rand_set_key(self.ctx, _p(None)))
+            return
+        key = np.frombuffer(bytes(key), dtype=np.uint8) if isinstance(key, (bytes, bytearray)) else _u8(key)
+        _need("gs_rand_set_key", [("key", key, 32)])
+        self._chk(self.lib.gs_rand_set_key(self.ctx, _p(key)))
+
+    @staticmethod
+    def _u64(fn, **vals):
+        for k, v in vals.items():
+            if not 0 <= v < (1 << (32 if k == "domain" else 64)):
+                raise GsError(3, "%s: %s does not fit its %d bits" % (fn, k, 32 if k == "domain" else 64))
+
+    def rand_fr_dev(self, domain, stream, first, count, out):
+        """count uniform Fr of (domain, stream), elements first .. first + count - 1, into a device tensor."""
+        self._u64("gs_rand_fr_dev", stream=stream, first=first, count=count, domain=domain)
+        _need("gs_rand_fr_dev", [("out", out, count * self.FR)])
+        self._chk(self.lib.gs_rand_fr_dev(self.ctx, domain, stream, first, count, _p(out)))
+
+    def rand_fr(self, domain, stream, first, count, out=None):
+        self._u64("gs_rand_fr", stream=stream, first=first, count=count, domain=domain)
+        if first + count > (1 << 32):  # (before the output is allocated: the C ABI refuses the same draw)
+            raise GsError(1, "gs_rand_fr: first + count > 2^32")
+        if out is None:
+            out = self._out(count * self.FR)
+        _need("gs_rand_fr", [("out", out, count * self.FR)])
+        self._chk(self.lib.gs_rand_fr(self.ctx, domain, stream, first, count, _p(out)))
+        return out
+
+    def rand_rho_dev(self, stream, first, count, out):
+        """count non-zero 64-bit exponents of the rho stream `stream` into a device tensor."""
+        self._u64("gs_rand_rho_dev", stream=stream, first=first, count=count)
+        _need("gs_rand_rho_dev", [("out", out, count * 8)])
+        self._chk(self.lib.gs_rand_rho_dev(self.ctx, stream, first, count, _p(out)))
+
+    def rand_rho(self, stream, first, count, out=None):
+        self._u64("gs_rand_rho", stream=stream, first=first, count=count)
+        if first + count > (1 << 35):
+            raise GsError(1, "gs_rand_rho: (first + count + 7) div 8 > 2^32")
+        if out is None:
+            out = np.zeros(count, dtype=np.uint64)
+        _need("gs_rand_rho", [("out", out, count * 8)])
+        self._chk(self.lib.gs_rand_rho(self.ctx, stream, first, count, _p(out)))
+        return out
+
+    def _prove_drawn(self, fn, ty, N, m, n, X, Y, A, B, Gamma, stream, rst=None, outs=None, want_coms=True,
+                     want_rand=True, out=None):
+        """gs_prove_*_drawn, host and _dev forms: the length checks of the siblings, then the call.  A host form
+        allocates its outputs (R, S, T too when want_rand) or writes into the preallocated uint8 arrays of the dict
+        `out` (keys R, S, T, xcoms, ycoms, pi, theta; pi and theta required); a _dev form takes rst = (R_out, S_out,
+        T_out), each may be None, and outs = (xcoms, ycoms, pi, theta), the first two may be None."""
+        dev, shared = fn.endswith("_dev"), "_statement" in fn
+        ins = (X, Y, A, B, Gamma)
+        if any(a is None for a in ins):
+            raise GsError(3, "%s: every input array is required" % fn)
+        self._u64(fn, stream=stream)
+        if not dev:
+            ins = tuple(_u8(a) for a in ins)
+        want = self._check(fn, ty, N, m, n, shared, **dict(zip(("X", "Y", "A", "B", "Gamma"), ins)))
+        if dev:
+            rst = (None,) * 3 if rst is None else tuple(rst)
+            if outs is None or outs[2] is None or outs[3] is None:
+                raise GsError(3, "%s: pi and theta are required" % fn)
+        elif out is not None:
+            rst = tuple(out.get(k) for k in ("R", "S", "T"))
+            outs = tuple(out.get(k) for k in ("xcoms", "ycoms", "pi", "theta"))
+            if outs[2] is None or outs[3] is None:
+                raise GsError(3, "%s: out needs pi and theta" % fn)
+        else:
+            rst = tuple(self._out(want[k]) if want_rand else None for k in ("R", "S", "T"))
+            outs = (self._out(want["xcoms"]) if want_coms else None, self._out(want["ycoms"]) if want_coms else None,
+                    self._out(want["pi"]), self._out(want["theta"]))
+        names = ("R", "S", "T", "xcoms", "ycoms", "pi", "theta")
+        self._check(fn, ty, N, m, n, shared, **dict(zip(names, rst + tuple(outs))))
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, N, m, n, *[_p(a) for a in ins], stream,
+                                        *[_p(a) for a in rst + tuple(outs)]))
+        return dict(zip(names, rst + tuple(outs)))
+
+    def prove_batch_drawn(self, ty, N, m, n, X, Y, A, B, Gamma, stream, want_coms=True, want_rand=True, out=None):
+        """gs_prove_batch with R, S, T drawn on the device from (the installed key, stream); they come back under "R",
+        "S", "T" when want_rand.  `out`: preallocated arrays to write into, as prove_batch takes them."""
+        return self._prove_drawn("gs_prove_batch_drawn", ty, N, m, n, X, Y, A, B, Gamma, stream, want_coms=want_coms,
+                                 want_rand=want_rand, out=out)
+
+    def prove_statement_drawn(self, ty, E, m, n, X, Y, A, B, Gamma, stream, want_coms=True, want_rand=True, out=None):
+        return self._prove_drawn("gs_prove_statement_drawn", ty, E, m, n, X, Y, A, B, Gamma, stream,
+                                 want_coms=want_coms, want_rand=want_rand, out=out)
+
+    def prove_batch_drawn_dev(self, ty, N, m, n, X, Y, A, B, Gamma, stream, R_out, S_out, T_out, xcoms, ycoms, pi,
+                              theta):
+        self._prove_drawn("gs_prove_batch_drawn_dev", ty, N, m, n, X, Y, A, B, Gamma, stream, (R_out, S_out, T_out),
+                          (xcoms, ycoms, pi, theta))
+
+    def prove_statement_drawn_dev(self, ty, E, m, n, X, Y, A, B, Gamma, stream, R_out, S_out, T_out, xcoms, ycoms, pi,
+                                  theta):
+        self._prove_drawn("gs_prove_statement_drawn_dev", ty, E, m, n, X, Y, A, B, Gamma, stream,
+                          (R_out, S_out, T_out), (xcoms, ycoms, pi, theta))
+
+    def _rerand_drawn(self, fn, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, stream, rst=None, outs=None,
+                      want_rand=True):
+        """gs_rerandomize_*_drawn, host and _dev forms (see _prove_drawn); all four outputs are required."""
+        dev, shared = fn.endswith("_dev"), "_statement" in fn
+        ins = (A, B, Gamma, xcoms, ycoms, pi, theta)
+        if any(a is None for a in ins):
+            raise GsError(3, "%s: every input array is required" % fn)
+        self._u64(fn, stream=stream)
+        if not dev:
+            ins = tuple(_u8(a) for a in ins)
+        in_names = ("A", "B", "Gamma", "xcoms", "ycoms", "pi", "theta")
+        want = self._check(fn, ty, N, m, n, shared, **dict(zip(in_names, ins)))
+        if dev:
+            rst = (None,) * 3 if rst is None else tuple(rst)
+            if outs is None or any(o is None for o in outs):
+                raise GsError(3, "%s: every output array is required" % fn)
+        else:
+            rst = tuple(self._out(want[k]) if want_rand else None for k in ("R", "S", "T"))
+            outs = tuple(self._out(want[k]) for k in ("xcoms", "ycoms", "pi", "theta"))
+        self._check(fn, ty, N, m, n, shared, **dict(zip(("R", "S", "T", "xcoms_out", "ycoms_out", "pi_out", "theta_out"),
+                                                        rst + tuple(outs))))
+        self._chk(getattr(self.lib, fn)(self.ctx, ty, N, m, n, *[_p(a) for a in ins], stream,
+                                        *[_p(a) for a in rst + tuple(outs)]))
+        return dict(zip(("R", "S", "T", "xcoms", "ycoms", "pi", "theta"), rst + tuple(outs)))
+
+    def rerandomize_batch_drawn(self, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, stream, want_rand=True):
+        """gs_rerandomize_batch with R', S', T' drawn on the device from (the installed key, stream)."""
+        return self._rerand_drawn("gs_rerandomize_batch_drawn", ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
+                                  stream, want_rand=want_rand)
+
+    def rerandomize_statement_drawn(self, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, stream, want_rand=True):
+        return self._rerand_drawn("gs_rerandomize_statement_drawn", ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
+                                  stream, want_rand=want_rand)
+
+    def rerandomize_batch_drawn_dev(self, ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, stream, R_out, S_out,
+                                    T_out, xcoms_out, ycoms_out, pi_out, theta_out):
+        self._rerand_drawn("gs_rerandomize_batch_drawn_dev", ty, N, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, stream,
+                           (R_out, S_out, T_out), (xcoms_out, ycoms_out, pi_out, theta_out))
+
+    def rerandomize_statement_drawn_dev(self, ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta, stream, R_out, S_out,
+                                        T_out, xcoms_out, ycoms_out, pi_out, theta_out):
+        self._rerand_drawn("gs_rerandomize_statement_drawn_dev", ty, E, m, n, A, B, Gamma, xcoms, ycoms, pi, theta,
+                           stream, (R_out, S_out, T_out), (xcoms_out, ycoms_out, pi_out, theta_out))
 
     def set_extraction_key(self, key):
         """Install the binding key (a1, a2) of the installed CRS: two Montgomery Fr (gs_set_extraction_key); None

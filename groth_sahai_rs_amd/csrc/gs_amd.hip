@@ -29,6 +29,7 @@
 #include "gs_params_bls12_381.h"
 #include "gs_params_bn254.h"
 #include "gs_kernels.cuh"
+#include "gs_rand.cuh"
 #include "gs_layout.h"
 
 namespace gs {
@@ -148,6 +149,10 @@ struct gs_ctx {
   // A secret like the binding key: zeroed when the key goes (clear_simulation_key).
   DevBuf skey;
   bool have_skey = false;
+  // ChaCha20 key of the device generator (gs_rand_set_key): 32 bytes in device memory, read by k_rand_fr / k_rand_rho
+  // alone.  A secret like the two above, but not tied to the CRS: zeroed when the key goes (clear_rand_key).
+  DevBuf rkey;
+  bool have_rkey = false;
   // baby-step tables of gs_dlog_prepare, one per group ([0] G1, [1] G2): public data, not tied to the CRS
   struct DlogTab {
     DevBuf slots;  // 2^(log2_table + 1) x u64
@@ -3121,6 +3126,16 @@ static void clear_simulation_key(gs_ctx* c) {
   hipStreamSynchronize(c->stream);
 }
 
+// Forget the generator's key: the context's copy is zeroed on the stream, behind the draws already enqueued.
+static void clear_rand_key(gs_ctx* c) {
+  c->have_rkey = false;
+  if (!c->rkey.p) return;
+  hipSetDevice(c->device);
+  drain_ctx(c);
+  hipMemsetAsync(c->rkey.p, 0, c->rkey.cap, c->stream);
+  hipStreamSynchronize(c->stream);
+}
+
 static int check_ctx(gs_ctx* c, bool need_crs) {
   if (!c) return GS_ERR_ARG;
   hipError_t e = hipSetDevice(c->device);
@@ -3328,6 +3343,12 @@ template <class C> static int set_simulation_key_impl(gs_ctx* c, const void* key
   c->have_skey = true;
   return GS_OK;
 }
+// ---- randomness drawn on the device (gs_rand.cuh; entry points below) -------------------------------------------------
+template <class C>
+static int rand_fr_impl(gs_ctx* c, uint32_t domain, uint64_t stream, uint64_t first, size_t count, void* out) {
+  return launch(c, "k_rand_fr", k_rand_fr<C>, count, RAND_BLOCK, count, (const uint32_t*)c->rkey.p, domain, stream, first,
+                (Fr<C>*)out);
+}
 template <class C, class F> static int extract_impl(gs_ctx* c, const char* name, int slot, size_t n, const void* coms, void* out) {
   const SharedDigits* sd = (const SharedDigits*)c->xkey.p + slot;
   if (c->endo)
@@ -3406,6 +3427,8 @@ void gs_ctx_destroy(gs_ctx* c) {
   if (c->xkey.p) hipFree(c->xkey.p);
   clear_simulation_key(c);
   if (c->skey.p) hipFree(c->skey.p);
+  clear_rand_key(c);
+  if (c->rkey.p) hipFree(c->rkey.p);
   for (auto& t : c->dlog)
     for (DevBuf* b : {&t.slots, &t.aux})
       if (b->p) hipFree(b->p);
@@ -3739,6 +3762,7 @@ struct BatchArgs {
   int m, n;
   bool shared;  // a Statement('s part): ONE copy of X, Y, R, S and of the commitments for all N equations
   const void* p[14];
+  uint64_t stream = 0;  // the drawn entries: the generator's stream number of this call
   void* out(int slot) const { return const_cast<void*>(p[slot]); }
 };
 // An operation states its arrays ONCE: HostPipe slot (= index into BatchArgs::p), which entry of the layout table
@@ -4237,6 +4261,189 @@ int gs_set_simulation_key(gs_ctx* c, const void* t1t2) {
   if (rc != GS_OK) clear_simulation_key(c);  // a refused key leaves nothing behind
   return rc;
 }
+
+// ---- randomness drawn on the device: the keyed ChaCha20 of gs_rand.cuh ------------------------------------------------
+int gs_rand_set_key(gs_ctx* c, const void* key32) {
+  RC(check_ctx(c, false));
+  if (c->rec) return fail(c, GS_ERR_ARG, "gs_rand_set_key inside a mixed call");
+  clear_rand_key(c);
+  if (!key32) return GS_OK;
+  RC(ensure(c, c->rkey, 32));
+  // Straight from the caller's buffer into the context's copy: the library keeps no staged copy of this key.  The
+  // stream is drained first (draws under the old key, the memset above) and the copy is complete on return.
+  hipError_t e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(c->rkey.p, key32, 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess) {
+    clear_rand_key(c);  // (rkey.p is set: whatever arrived is zeroed)
+    return fail(c, GS_ERR_DEVICE, "gs_rand_set_key", e);
+  }
+  c->have_rkey = true;
+  return GS_OK;
+}
+static const uint64_t RAND_COUNTERS = (uint64_t)1 << 32;  // block counters of one (domain, stream): the counter never wraps
+static int rand_check(gs_ctx* c, const char* fn) {
+  RC(check_ctx(c, false));
+  if (c->rec) return fail(c, GS_ERR_ARG, (std::string(fn) + " inside a mixed call").c_str());
+  if (!c->have_rkey) return fail(c, GS_ERR_ARG, (std::string(fn) + ": gs_rand_set_key has not been called").c_str());
+  return GS_OK;
+}
+// count Fr of (domain, stream) from element `first` into device memory, on the current stream
+static int rand_fr_launch(gs_ctx* c, uint32_t domain, uint64_t stream, uint64_t first, size_t count, void* out) {
+  if (first > RAND_COUNTERS || (uint64_t)count > RAND_COUNTERS - first)
+    return fail(c, GS_ERR_SHAPE, "gs_rand_fr: first + count > 2^32 (one block per scalar, 32-bit block counter)");
+  return DISPATCH_FN(c, rand_fr_impl, (c, domain, stream, first, count, out));
+}
+static int rand_fr_call(gs_ctx* c, const char* fn, bool host, uint32_t domain, uint64_t stream, uint64_t first,
+                        size_t count, void* out) {
+  RC(rand_check(c, fn));
+  if (first > RAND_COUNTERS || (uint64_t)count > RAND_COUNTERS - first)
+    return fail(c, GS_ERR_SHAPE, "gs_rand_fr: first + count > 2^32 (one block per scalar, 32-bit block counter)");
+  if (count == 0) return GS_OK;
+  if (!out) return fail(c, GS_ERR_ARG, "null pointer");
+  if (!host) return rand_fr_launch(c, domain, stream, first, count, out);
+  return staged_call(c, {}, {{out, count * SZ_FR}},
+                     [&](void** d) { return rand_fr_launch(c, domain, stream, first, count, d[0]); });
+}
+int gs_rand_fr_dev(gs_ctx* c, uint32_t domain, uint64_t stream, uint64_t first, size_t count, void* out) {
+  return rand_fr_call(c, "gs_rand_fr_dev", false, domain, stream, first, count, out);
+}
+int gs_rand_fr(gs_ctx* c, uint32_t domain, uint64_t stream, uint64_t first, size_t count, void* out) {
+  return rand_fr_call(c, "gs_rand_fr", true, domain, stream, first, count, out);
+}
+static int rand_rho_call(gs_ctx* c, const char* fn, bool host, uint64_t stream, uint64_t first, size_t count,
+                         uint64_t* out) {
+  RC(rand_check(c, fn));
+  // blocks first div 8 .. (first + count - 1) div 8, all below 2^32 (first + count itself must not wrap either)
+  if (first > 8 * RAND_COUNTERS || (uint64_t)count > 8 * RAND_COUNTERS - first)
+    return fail(c, GS_ERR_SHAPE, "gs_rand_rho: (first + count + 7) div 8 > 2^32 (eight exponents per block, 32-bit block counter)");
+  if (count == 0) return GS_OK;
+  if (!out) return fail(c, GS_ERR_ARG, "null pointer");
+  const size_t nblocks = (size_t)((first + count + 7) / 8 - first / 8);
+  auto go = [&](uint64_t* d) {
+    return launch(c, "k_rand_rho", k_rand_rho, nblocks, RAND_BLOCK, nblocks, (const uint32_t*)c->rkey.p, stream, first,
+                  (uint64_t)count, d);
+  };
+  if (!host) return go(out);
+  return staged_call(c, {}, {{out, count * sizeof(uint64_t)}}, [&](void** d) { return go((uint64_t*)d[0]); });
+}
+int gs_rand_rho_dev(gs_ctx* c, uint64_t stream, uint64_t first, size_t count, uint64_t* out) {
+  return rand_rho_call(c, "gs_rand_rho_dev", false, stream, first, count, out);
+}
+int gs_rand_rho(gs_ctx* c, uint64_t stream, uint64_t first, size_t count, uint64_t* out) {
+  return rand_rho_call(c, "gs_rand_rho", true, stream, first, count, out);
+}
+
+// The drawn forms of prove and rerandomize: the sibling's arrays with R, S, T as optional OUTPUTS, and a run that draws
+// the three arrays (asked for: into the caller's / the pipe's buffer; else into scratch that is zeroed behind the
+// sibling's kernels) and then runs the sibling.  sr = the slot of R (S and T follow it), dom = the domain of R.
+static_assert(PI_S == PI_R + 1 && PI_T == PI_R + 2 && RI_S == RI_R + 1 && RI_T == RI_R + 2, "R, S, T are consecutive slots");
+static_assert(GS_RAND_PROVE_S == GS_RAND_PROVE_R + 1 && GS_RAND_PROVE_T == GS_RAND_PROVE_R + 2 &&
+                  GS_RAND_RERAND_S == GS_RAND_RERAND_R + 1 && GS_RAND_RERAND_T == GS_RAND_RERAND_R + 2,
+              "the domains of R, S, T are consecutive");
+static int drawn_run(gs_ctx* c, const BatchArgs& a, const Op& sibling, int sr, uint32_t dom) {
+  static const char* const names[3] = {"drawn.R", "drawn.S", "drawn.T"};
+  static const lay::Array arrs[3] = {lay::R, lay::S, lay::T};
+  const lay::Layout L = layout_of(c, a);
+  struct Wipe {  // whatever happens below: on the stream, after the kernels enqueued so far
+    gs_ctx* c;
+    void* p[3];
+    size_t bytes[3];
+    ~Wipe() {
+      for (int k = 0; k < 3; k++)
+        if (p[k]) hipMemsetAsync(p[k], 0, bytes[k], c->stream);
+    }
+  } wipe{c, {nullptr, nullptr, nullptr}, {0, 0, 0}};
+  BatchArgs d = a;
+  for (int k = 0; k < 3; k++) {
+    const size_t bytes = L.bytes[arrs[k]];
+    void* p = a.out(sr + k);
+    if (!p) {
+      RC(scratch(c, names[k], bytes, &p));
+      wipe.p[k] = p, wipe.bytes[k] = bytes;
+      d.p[sr + k] = p;
+    }
+    RC(rand_fr_launch(c, dom + k, a.stream, 0, bytes / SZ_FR, p));
+  }
+  return sibling.run(c, d);
+}
+static const ArrDesc kProveDrawnArrs[] = {
+    {PI_X, lay::X, ARR_IN},      {PI_Y, lay::Y, ARR_IN},      {PI_A, lay::A, ARR_IN},
+    {PI_B, lay::B, ARR_IN},      {PI_G, lay::GAMMA, ARR_IN},  {PI_R, lay::R, ARR_OUT | ARR_OPT},
+    {PI_S, lay::S, ARR_OUT | ARR_OPT}, {PI_T, lay::T, ARR_OUT | ARR_OPT}, {PO_XC, lay::XCOMS, ARR_OUT | ARR_OPT},
+    {PO_YC, lay::YCOMS, ARR_OUT | ARR_OPT}, {PO_PI, lay::PI, ARR_OUT}, {PO_TH, lay::THETA, ARR_OUT}};
+static const int* prove_drawn_order(int) {
+  static const int order[] = {PI_G, PI_Y, PI_B, PI_X, PI_A};  // prove_order without the scalars that are drawn
+  return order;
+}
+static int prove_drawn_run(gs_ctx* c, const BatchArgs& a) { return drawn_run(c, a, kProve, PI_R, GS_RAND_PROVE_R); }
+static const Op kProveDrawn = {kProveDrawnArrs, sizeof kProveDrawnArrs / sizeof *kProveDrawnArrs, prove_drawn_order, 5,
+                               prove_drawn_run};
+static const ArrDesc kRerandDrawnArrs[] = {
+    {RI_A, lay::A, ARR_IN},       {RI_B, lay::B, ARR_IN},       {RI_G, lay::GAMMA, ARR_IN},
+    {RI_R, lay::R, ARR_OUT | ARR_OPT}, {RI_S, lay::S, ARR_OUT | ARR_OPT}, {RI_T, lay::T, ARR_OUT | ARR_OPT},
+    {RI_XC, lay::XCOMS, ARR_IN},  {RI_YC, lay::YCOMS, ARR_IN},  {RI_PI, lay::PI, ARR_IN},   {RI_TH, lay::THETA, ARR_IN},
+    {RO_XC, lay::XCOMS, ARR_OUT}, {RO_YC, lay::YCOMS, ARR_OUT}, {RO_PI, lay::PI, ARR_OUT},  {RO_TH, lay::THETA, ARR_OUT}};
+static const int* rerand_drawn_order(int) {
+  static const int order[] = {RI_G, RI_B, RI_A, RI_YC, RI_PI, RI_XC, RI_TH};  // rerand_order without the scalars
+  return order;
+}
+static int rerand_drawn_run(gs_ctx* c, const BatchArgs& a) { return drawn_run(c, a, kRerand, RI_R, GS_RAND_RERAND_R); }
+static const Op kRerandDrawn = {kRerandDrawnArrs, sizeof kRerandDrawnArrs / sizeof *kRerandDrawnArrs, rerand_drawn_order, 7,
+                                rerand_drawn_run};
+static int drawn_call(gs_ctx* c, const char* fn, const Op& op, bool host, const BatchArgs& a) {
+  if (c && c->rec) return fail(c, GS_ERR_ARG, (std::string(fn) + " inside a mixed call").c_str());
+  RC(batch_check(c, op, a));
+  if (!c->have_rkey) return fail(c, GS_ERR_ARG, (std::string(fn) + ": gs_rand_set_key has not been called").c_str());
+  if (a.N == 0) return GS_OK;
+  const lay::Layout L = layout_of(c, a);
+  for (lay::Array r : {lay::R, lay::S, lay::T})
+    if (L.bytes[r] / SZ_FR > RAND_COUNTERS)
+      return fail(c, GS_ERR_SHAPE, (std::string(fn) + ": more than 2^32 scalars in one of R, S, T").c_str());
+  if (!host) return op.run(c, a);
+  // outputs do not alias inputs or each other (the staged copies would hide it; the device form's contract)
+  for (int oi = 0; oi < op.narrs; oi++) {
+    const ArrDesc& o = op.arrs[oi];
+    if (!(o.flags & ARR_OUT) || !a.p[o.slot]) continue;
+    for (int ii = 0; ii < op.narrs; ii++) {
+      const ArrDesc& i = op.arrs[ii];
+      if (i.slot == o.slot || !a.p[i.slot]) continue;
+      uintptr_t x = (uintptr_t)a.p[o.slot], y = (uintptr_t)a.p[i.slot];
+      if (x < y + L.bytes[i.arr] && y < x + L.bytes[o.arr])
+        return fail(c, GS_ERR_ARG, (std::string(fn) + ": an output overlaps another array").c_str());
+    }
+  }
+  return batch_host_checked(c, op, a);
+}
+static BatchArgs with_stream(BatchArgs a, uint64_t stream) {
+  a.stream = stream;
+  return a;
+}
+#define GS_PROVE_DRAWN_ENTRY(NAME, HOST, SHARED)                                                                      \
+  int NAME(gs_ctx* c, int ty, size_t N, int m, int n, const void* X, const void* Y, const void* A, const void* B,      \
+           const void* G, uint64_t stream, void* R, void* S, void* T, void* xcoms, void* ycoms, void* pi, void* theta) { \
+    return drawn_call(c, #NAME, kProveDrawn, HOST,                                                                     \
+                      with_stream(BatchArgs{ty, N, m, n, SHARED, {X, Y, A, B, G, R, S, T, xcoms, ycoms, pi, theta}}, stream)); \
+  }
+GS_PROVE_DRAWN_ENTRY(gs_prove_batch_drawn_dev, false, false)
+GS_PROVE_DRAWN_ENTRY(gs_prove_batch_drawn, true, false)
+GS_PROVE_DRAWN_ENTRY(gs_prove_statement_drawn_dev, false, true)
+GS_PROVE_DRAWN_ENTRY(gs_prove_statement_drawn, true, true)
+#undef GS_PROVE_DRAWN_ENTRY
+#define GS_RERAND_DRAWN_ENTRY(NAME, HOST, SHARED)                                                                     \
+  int NAME(gs_ctx* c, int ty, size_t N, int m, int n, const void* A, const void* B, const void* G, const void* xcoms,  \
+           const void* ycoms, const void* pi, const void* theta, uint64_t stream, void* R, void* S, void* T,          \
+           void* xcoms_out, void* ycoms_out, void* pi_out, void* theta_out) {                                         \
+    return drawn_call(c, #NAME, kRerandDrawn, HOST,                                                                    \
+                      with_stream(rerand_args(ty, N, m, n, SHARED, A, B, G, xcoms, ycoms, pi, theta, R, S, T, xcoms_out, \
+                                              ycoms_out, pi_out, theta_out),                                          \
+                                  stream));                                                                            \
+  }
+GS_RERAND_DRAWN_ENTRY(gs_rerandomize_batch_drawn_dev, false, false)
+GS_RERAND_DRAWN_ENTRY(gs_rerandomize_batch_drawn, true, false)
+GS_RERAND_DRAWN_ENTRY(gs_rerandomize_statement_drawn_dev, false, true)
+GS_RERAND_DRAWN_ENTRY(gs_rerandomize_statement_drawn, true, true)
+#undef GS_RERAND_DRAWN_ENTRY
 
 // ---- witness extraction with the binding key ---------------------------------------
 int gs_set_extraction_key(gs_ctx* c, const void* a1a2) {

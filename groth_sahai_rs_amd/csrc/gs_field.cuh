@@ -53,6 +53,7 @@ template <class C> struct FrM {
   GS_HD static uint32_t mod(int i) { return C::Q[i]; }
   GS_HD static uint32_t one(int i) { return C::Q_ONE[i]; }
   GS_HD static uint32_t r2(int i) { return C::Q_R2[i]; }
+  GS_HD static uint32_t r3(int i) { return C::Q_R3[i]; }
 };
 
 // Storage is a plain limb array (tight 4*N bytes, memcpy-compatible with the

@@ -15,6 +15,7 @@ top of the C ABI (same names, argument meaning and error behaviour):
     extract_scalars(commit, crs, key, bits, log2_table=None)              (new) committed scalars < 2^bits back themselves
     generate_crs_with_trapdoor -> (hiding CRS, trapdoor), <Equation>.simulate(crs, trapdoor, rng), Statement.simulate,
     equivocate(x, r, x_new, t)                                            (new) proofs without a witness, hiding CRS
+    DeviceRng(engine, key)                                                (new) as `rng`: R, S, T are drawn on the device
     EquProof {pi, theta, equ_type, rand}, CProof {xcoms, ycoms, equ_proofs} prove.rs:55-69
 
 Values are numpy uint64 limb arrays in the boundary layout of include/gs_amd.h
@@ -127,6 +128,34 @@ def extract_scalars(commit, crs, key, bits, log2_table=None):
         return []
     xs, found = crs.engine.extract_scalar(group, _cat(commit.coms, 0), bits)
     return [xs[i].view(np.uint64).copy() if found[i] else None for i in range(n)]
+
+
+class DeviceRng:
+    """Randomness drawn ON the device (include/gs_amd.h, "randomness drawn on the device"): installs the 32-byte
+    ChaCha20 `key` in `engine` and hands out stream numbers 0, 1, 2, ... -- one per call, as the contract demands (a
+    reused (key, stream) pair repeats the randomness and links the proofs).  Given as `rng` to
+    <Equation>.commit_and_prove, Statement.commit_and_prove or rerandomize, the call goes through the drawn entry
+    (gs_prove_batch_drawn, gs_prove_statement_drawn, gs_rerandomize_batch_drawn): R, S, T are generated in device
+    memory and come back with the proof, so the returned objects carry them like any other.  The results are NOT the
+    reference's for any rng state; with any other rng nothing changes.  The key must come from a CSPRNG."""
+
+    def __init__(self, engine, key, first_stream=0):
+        self.engine, self.stream = engine, first_stream
+        engine.rand_set_key(key)
+
+    def next_stream(self):
+        self.stream += 1
+        return self.stream - 1
+
+    def _for(self, crs):
+        assert crs.engine is self.engine, "the DeviceRng's key is installed in another engine than the CRS's"
+        return self.next_stream()
+
+
+def _mat(buf, rows, cols):
+    """flat Montgomery scalars -> Matrix<Fr> as the mirror objects hold it"""
+    a = np.asarray(buf).view(np.uint64).reshape(rows, cols, 4)
+    return [[a[i, j].copy() for j in range(cols)] for i in range(rows)]
 
 
 class Commit1:
@@ -268,6 +297,8 @@ class _Equation:
 
     def commit_and_prove(self, xvars, yvars, crs, rng):  # prove.rs:72-90 etc.
         kx, ky = self._kxky()
+        if isinstance(rng, DeviceRng):
+            return Statement([self]).commit_and_prove(xvars, yvars, crs, rng)  # (E = 1: the same draws, the same bytes)
         xcoms = (batch_commit_G1 if kx == 2 else batch_commit_scalar_to_B1)(xvars, crs, rng)
         ycoms = (batch_commit_G2 if ky == 2 else batch_commit_scalar_to_B2)(yvars, crs, rng)
         return CProof(xcoms, ycoms, [self.prove(xvars, yvars, xcoms, ycoms, crs, rng)])
@@ -352,13 +383,20 @@ def rerandomize(equ, com_proof, crs, rng):
     equ._check_statement_shape(m, n)
     # lengths that come from the wire are checked before a pointer crosses the C ABI
     assert len(pf.pi) == kx and len(pf.theta) == ky
-    R1 = [[rng.fr() for _ in range(kx)] for _ in range(m)]
-    S1 = [[rng.fr() for _ in range(ky)] for _ in range(n)]
-    T1 = [[rng.fr() for _ in range(kx)] for _ in range(ky)]
-    out = crs.engine.rerandomize_batch(equ.TYPE, 1, m, n, _cat(equ.a_consts, 0), _cat(equ.b_consts, 0),
-                                       _flat_mat(equ.gamma), _cat(com_proof.xcoms.coms, 0),
-                                       _cat(com_proof.ycoms.coms, 0), _cat(pf.pi, 0), _cat(pf.theta, 0),
-                                       _flat_mat(R1), _flat_mat(S1), _flat_mat(T1))
+    if isinstance(rng, DeviceRng):  # R', S', T' are drawn on the device and come back with the proof
+        out = crs.engine.rerandomize_batch_drawn(equ.TYPE, 1, m, n, _cat(equ.a_consts, 0), _cat(equ.b_consts, 0),
+                                                 _flat_mat(equ.gamma), _cat(com_proof.xcoms.coms, 0),
+                                                 _cat(com_proof.ycoms.coms, 0), _cat(pf.pi, 0), _cat(pf.theta, 0),
+                                                 rng._for(crs))
+        R1, S1, T1 = _mat(out["R"], m, kx), _mat(out["S"], n, ky), _mat(out["T"], ky, kx)
+    else:
+        R1 = [[rng.fr() for _ in range(kx)] for _ in range(m)]
+        S1 = [[rng.fr() for _ in range(ky)] for _ in range(n)]
+        T1 = [[rng.fr() for _ in range(kx)] for _ in range(ky)]
+        out = crs.engine.rerandomize_batch(equ.TYPE, 1, m, n, _cat(equ.a_consts, 0), _cat(equ.b_consts, 0),
+                                           _flat_mat(equ.gamma), _cat(com_proof.xcoms.coms, 0),
+                                           _cat(com_proof.ycoms.coms, 0), _cat(pf.pi, 0), _cat(pf.theta, 0),
+                                           _flat_mat(R1), _flat_mat(S1), _flat_mat(T1))
     xr, yr, tr = com_proof.xcoms.rand, com_proof.ycoms.rand, pf.rand
     if xr is not None and yr is not None and tr is not None:
         r = _FR_ORDER[crs.engine.curve]
@@ -485,14 +523,20 @@ class Statement:
         assert m >= 1 and n >= 1
         for equ in self.equations:
             equ._check_statement_shape(m, n)
-        R = [[rng.fr() for _ in range(kx)] for _ in range(m)]
-        S = [[rng.fr() for _ in range(ky)] for _ in range(n)]
-        Ts = [[[rng.fr() for _ in range(kx)] for _ in range(ky)] for _ in range(E)]
         cat = np.concatenate
-        out = crs.engine.prove_statement(
-            self.TYPE, E, m, n, _cat(xvars, 0), _cat(yvars, 0), cat([_cat(e.a_consts, 0) for e in self.equations]),
-            cat([_cat(e.b_consts, 0) for e in self.equations]), cat([_flat_mat(e.gamma) for e in self.equations]),
-            _flat_mat(R), _flat_mat(S), cat([_flat_mat(T) for T in Ts]))
+        consts = (cat([_cat(e.a_consts, 0) for e in self.equations]), cat([_cat(e.b_consts, 0) for e in self.equations]),
+                  cat([_flat_mat(e.gamma) for e in self.equations]))
+        if isinstance(rng, DeviceRng):  # R, S, T are drawn on the device and come back with the proofs
+            out = crs.engine.prove_statement_drawn(self.TYPE, E, m, n, _cat(xvars, 0), _cat(yvars, 0), *consts,
+                                                   rng._for(crs))
+            R, S = _mat(out["R"], m, kx), _mat(out["S"], n, ky)
+            Ts = [_mat(np.asarray(out["T"]).reshape(E, -1)[e], ky, kx) for e in range(E)]
+        else:
+            R = [[rng.fr() for _ in range(kx)] for _ in range(m)]
+            S = [[rng.fr() for _ in range(ky)] for _ in range(n)]
+            Ts = [[[rng.fr() for _ in range(kx)] for _ in range(ky)] for _ in range(E)]
+            out = crs.engine.prove_statement(self.TYPE, E, m, n, _cat(xvars, 0), _cat(yvars, 0), *consts,
+                                             _flat_mat(R), _flat_mat(S), cat([_flat_mat(T) for T in Ts]))
         xcoms = Commit1(_split(out["xcoms"], m), R)
         ycoms = Commit2(_split(out["ycoms"], n), S)
         pis, ths = _split(out["pi"], E * kx), _split(out["theta"], E * ky)

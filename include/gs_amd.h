@@ -38,8 +38,11 @@
  *   GS_MSMEG2 : x in Fr^m, Y in G2^n, a in Fr^n, B in G2^m, target G2,  kx=1, ky=2
  *   GS_QUAD   : x in Fr^m, y in Fr^n, a in Fr^n, b in Fr^m, target Fr,  kx=1, ky=1
  *
- * Randomness (R, S, T) is ALWAYS an input: the shim draws it from the caller's
- * Rng in the reference's order (R row-major, then S, then T).
+ * Randomness (R, S, T) is an input of every entry point that computes what the
+ * reference computes: the shim draws it from the caller's Rng in the reference's
+ * order (R row-major, then S, then T).  The *_drawn forms of prove and rerandomize
+ * draw it on the device from a keyed ChaCha20 instead ("randomness drawn on the
+ * device" below); their outputs are NOT the reference's for any rng state.
  *
  * Pointers: the *_dev entry points take DEVICE pointers (hipMalloc'ed, 16-byte
  * aligned) and enqueue on the context's stream without synchronising; the
@@ -391,6 +394,110 @@ int gs_simulate_statement_dev(gs_ctx*, int equ_type, size_t E, int m, int n, con
 int gs_simulate_statement(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B, const void* Gamma,
                           const void* target, const void* Rc, const void* Sc, const void* Tf, void* xcoms, void* ycoms,
                           void* pi, void* theta);
+
+/* ---- randomness drawn on the device (a keyed, counter-addressed ChaCha20) --------------------------------------------
+ * The entry points above take their secret scalars R, S, T (and the verifiers their rho) as arrays the caller has drawn.
+ * These draw them in device memory instead: nothing is drawn on a host thread and nothing is staged across PCIe.
+ *
+ * The generator is the ChaCha20 block function of RFC 8439 section 2.3 (20 rounds, 32-bit block counter in state word
+ * 12, 96-bit nonce in words 13..15) under a 32-byte key (state words 4..11, little-endian) and the nonce
+ * LE32(domain) || LE64(stream).  The block counter is the element's block index and there is no running state: element
+ * i of a draw is a pure function of (key, domain, stream, i), whatever the launch shape, so a shard draws its slice of a
+ * global array by passing `first`.
+ *   Fr   one block per scalar, element i = block first + i.  The 64 output bytes are a 512-bit little-endian integer v;
+ *        the scalar is v mod r (bias below 2^-256 on both curves), written as every entry point takes an Fr (4 u64 limbs
+ *        of x 2^256 mod r).
+ *   rho  eight little-endian u64 per block under the domain GS_RAND_RHO: element j = word (first + j) mod 8 of block
+ *        (first + j) div 8.  A zero word is replaced by 1 (bias 2^-64): the rho contract of the *_rlc verifiers demands
+ *        non-zero exponents and their _dev forms cannot look.
+ * Domains: the library's own are the enum below; a caller's own draws use domains >= GS_RAND_USER.  gs_rand_fr[_dev]
+ * accepts ANY domain, the library's included -- that is what defines the drawn entries and makes them testable.
+ *
+ * gs_rand_set_key: key32 is a HOST pointer to 32 bytes; NULL forgets the key.  The key is a SECRET, handled as
+ * gs_set_simulation_key handles its own: it goes from the caller's buffer straight into the context's device copy (the
+ * library keeps no staged copy that could outlive the call), and that copy is zeroed on gs_rand_set_key(NULL), on
+ * replacement, when the upload fails and on gs_ctx_destroy.  It is not tied to the CRS (no CRS is needed, and
+ * gs_set_crs leaves it alone).  The call synchronises the stream.  The caller's own buffer is the caller's to wipe.
+ *
+ * THE CONTRACT.  The key comes from a CSPRNG.  A (key, stream) pair is used for ONE call of ONE operation: a reused
+ * pair repeats the randomness, which links the proofs and breaks witness-indistinguishability (two proofs under the same
+ * R, S, T reveal differences of witnesses).  A rho stream is drawn AFTER the batch to be verified is fixed, and the key
+ * stays secret until the verdict is out: whoever knows rho before choosing the proofs can cancel a forgery.
+ *
+ * gs_rand_fr / gs_rand_rho write `count` elements to out (host pointer; _dev: device pointer, only enqueued).
+ * Errors: GS_ERR_ARG while no key is installed, for a null out, and inside a mixed call.  GS_ERR_SHAPE when the draw
+ * would need a block counter >= 2^32 -- first + count > 2^32 for Fr, (first + count + 7) div 8 > 2^32 for rho; the
+ * counter never wraps and nothing is written.  count == 0 is a no-op.
+ *
+ * The DRAWN forms of prove and rerandomize take a stream number where their siblings take R, S, T:
+ *   gs_prove_batch_drawn_dev(..., stream, R_out, S_out, T_out, ...) writes, byte for byte, what gs_prove_batch_dev writes for
+ *     R = gs_rand_fr(GS_RAND_PROVE_R, stream, 0, N m kx)   S = gs_rand_fr(GS_RAND_PROVE_S, stream, 0, N n ky)
+ *     T = gs_rand_fr(GS_RAND_PROVE_T, stream, 0, N ky kx)
+ *   in the layouts of gs_prove_batch (element index = flat array index).  The statement forms draw R[m][kx], S[n][ky]
+ *   once and T[E][ky][kx]; the rerandomize forms are the same over GS_RAND_RERAND_R/S/T.  The host forms compute what
+ *   the _dev forms compute.
+ * R_out, S_out, T_out may each be NULL: a prover that later opens or rerandomizes needs them, a mix server does not.
+ * Arrays not asked for live in the context's scratch and are zeroed on the stream behind the last kernel that reads
+ * them.  In the host forms R, S, T are never staged in: they come back with the other outputs when asked for.
+ * Errors: GS_ERR_ARG while no key is installed, inside a mixed call, and (host forms) when an output overlaps an input or
+ * another output; GS_ERR_SHAPE when one of the three arrays has more than 2^32 scalars; N == 0 is a no-op; shapes and
+ * the remaining errors are those of gs_prove_batch / gs_rerandomize_batch.
+ * OUT OF SCOPE: there are no drawn forms of gs_simulate_*, of the mixed calls or of the gs_multi_* handles.  Those
+ * callers compose gs_rand_fr_dev (first = their global offset, on a shard's context) with the existing _dev entries.
+ * How it is computed: "k_rand_fr" (one lane per scalar: the block, then two 8-limb Montgomery products
+ * by R^2 and R^3 mod r and one modular addition) and "k_rand_rho" (one lane per block), 256-thread blocks, the key read
+ * through scalar loads; then the kernels of gs_prove_batch_dev / gs_rerandomize_batch_dev, unchanged.
+ * WHEN TO CALL IT: whenever the caller does not need the reference's outputs for a given rng state (parity: the entries
+ * that take R, S, T).  Measured (tools/rand_rate.py, profiles/rand/rate.json, DESIGN.md 6.10: one MI355X, BLS12-381,
+ * PPE 4 x 4, median of 7 after a warm-up, the entries alternating, every entry writing into the same preallocated
+ * arrays), ms per call.  The generator alone, one call with launch and sync: the 20 N scalars of a prove 0.031 at
+ * N = 2^12 and 0.081 at 2^16 (1.31 M scalars), the 4 N exponents of a batched check 0.026 and 0.019.  Host pointers,
+ * gs_prove_batch_drawn with R_out = S_out = T_out = NULL against gs_prove_batch given ready-made arrays: 9.41 against
+ * 9.53 at 2^12 (ratio 0.987, the yardstick's own spread 0.063), 71.69 against 73.01 at 2^16 (0.982, spread 0.025; 41.9 MB
+ * of scalars not staged); with all three returned 9.48 (0.995) and 72.30 (0.990).  Device pointers, against
+ * gs_prove_batch_dev: 8.01 against 7.90 at 2^12 (1.014, spread 0.051) and 65.06 against 64.75 at 2^16 (1.005, spread
+ * 0.009); returned 8.02 (1.016) and 64.93 (1.003): three more launches and the zeroing, inside the yardstick's spread
+ * in every row.  The drawn entry is not slower than its sibling anywhere it was measured; what it saves the CALLER --
+ * drawing 20 N scalars on a host thread before the call -- is not in these numbers and was not measured. */
+enum {
+  GS_RAND_PROVE_R = 0x0101, GS_RAND_PROVE_S = 0x0102, GS_RAND_PROVE_T = 0x0103,
+  GS_RAND_RERAND_R = 0x0201, GS_RAND_RERAND_S = 0x0202, GS_RAND_RERAND_T = 0x0203,
+  GS_RAND_RHO = 0x0301,
+  GS_RAND_USER = 0x10000 /* callers' own domains start here */
+};
+int gs_rand_set_key(gs_ctx*, const void* key32);
+int gs_rand_fr_dev(gs_ctx*, uint32_t domain, uint64_t stream, uint64_t first, size_t count, void* out_fr);
+int gs_rand_fr(gs_ctx*, uint32_t domain, uint64_t stream, uint64_t first, size_t count, void* out_fr);
+int gs_rand_rho_dev(gs_ctx*, uint64_t stream, uint64_t first, size_t count, uint64_t* out);
+int gs_rand_rho(gs_ctx*, uint64_t stream, uint64_t first, size_t count, uint64_t* out);
+int gs_prove_batch_drawn_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                             const void* B, const void* Gamma, uint64_t stream, void* R_out, void* S_out, void* T_out,
+                             void* xcoms, void* ycoms, void* pi, void* theta);
+int gs_prove_batch_drawn(gs_ctx*, int equ_type, size_t N, int m, int n, const void* X, const void* Y, const void* A,
+                         const void* B, const void* Gamma, uint64_t stream, void* R_out, void* S_out, void* T_out,
+                         void* xcoms, void* ycoms, void* pi, void* theta);
+int gs_prove_statement_drawn_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y,
+                                 const void* A, const void* B, const void* Gamma, uint64_t stream, void* R_out,
+                                 void* S_out, void* T_out, void* xcoms, void* ycoms, void* pi, void* theta);
+int gs_prove_statement_drawn(gs_ctx*, int equ_type, size_t E, int m, int n, const void* X, const void* Y, const void* A,
+                             const void* B, const void* Gamma, uint64_t stream, void* R_out, void* S_out, void* T_out,
+                             void* xcoms, void* ycoms, void* pi, void* theta);
+int gs_rerandomize_batch_drawn_dev(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                                   const void* Gamma, const void* xcoms, const void* ycoms, const void* pi,
+                                   const void* theta, uint64_t stream, void* R_out, void* S_out, void* T_out,
+                                   void* xcoms_out, void* ycoms_out, void* pi_out, void* theta_out);
+int gs_rerandomize_batch_drawn(gs_ctx*, int equ_type, size_t N, int m, int n, const void* A, const void* B,
+                               const void* Gamma, const void* xcoms, const void* ycoms, const void* pi, const void* theta,
+                               uint64_t stream, void* R_out, void* S_out, void* T_out, void* xcoms_out, void* ycoms_out,
+                               void* pi_out, void* theta_out);
+int gs_rerandomize_statement_drawn_dev(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B,
+                                       const void* Gamma, const void* xcoms, const void* ycoms, const void* pi,
+                                       const void* theta, uint64_t stream, void* R_out, void* S_out, void* T_out,
+                                       void* xcoms_out, void* ycoms_out, void* pi_out, void* theta_out);
+int gs_rerandomize_statement_drawn(gs_ctx*, int equ_type, size_t E, int m, int n, const void* A, const void* B,
+                                   const void* Gamma, const void* xcoms, const void* ycoms, const void* pi,
+                                   const void* theta, uint64_t stream, void* R_out, void* S_out, void* T_out,
+                                   void* xcoms_out, void* ycoms_out, void* pi_out, void* theta_out);
 
 /* ---- dlog (bounded scalar witnesses back from their images) --------------- */
 /* gs_extract_* opens a committed SCALAR to its image x * generator.  The scalars committed under Groth-Sahai (amounts,

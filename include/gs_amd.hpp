@@ -17,6 +17,8 @@
 //   CRS::dlog_prepare, CRS::extract_scalars                             (new) committed scalars < 2^bits back themselves
 //   CRS::generate_hiding_with_trapdoor, CRS::set_simulation_key, Equation::simulate, Statement::simulate
 //                                                                       (new) proofs without a witness, hiding CRS
+//   DeviceRng(crs, key32)                                               (new) as `rng` of commit_and_prove / rerandomize:
+//                                                                       R, S, T are drawn on the device (gs_*_drawn)
 //
 // Values are byte strings in the boundary layout of gs_amd.h (arkworks' Montgomery
 // limbs).  `Rng` is any type with `Fr fr()`; draws happen in the reference's order
@@ -29,6 +31,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -265,6 +268,27 @@ struct CRS {  // generator.rs:35-42
   }
 };
 
+// (new) Randomness drawn ON the device (gs_amd.h, "randomness drawn on the device"): installs the 32-byte ChaCha20 key in
+// the CRS's context and hands out stream numbers 0, 1, 2, ... -- one per call, as the contract demands (a reused
+// (key, stream) pair repeats the randomness and links the proofs).  Given as `rng` to Equation::commit_and_prove,
+// Equation::rerandomize or Statement::commit_and_prove, the call goes through the drawn entry: R, S, T are generated in
+// device memory and come back with the proof, so the returned objects carry them like any other.  The results are NOT
+// the reference's for any rng state; the key must come from a CSPRNG.  The caller's copy of the key is the caller's to
+// wipe.
+struct DeviceRng {
+  std::shared_ptr<Ctx> ctx;
+  uint64_t stream;
+  DeviceRng(const CRS& crs, const Bytes& key32, uint64_t first_stream = 0) : ctx(crs.ctx), stream(first_stream) {
+    assert_eq(key32.size(), 32, "the generator's key is 32 bytes");
+    ctx->chk(gs_rand_set_key(ctx->c, key32.data()));
+  }
+  // the stream number of the next call against `crs` (whose context must be the one that holds the key)
+  uint64_t next_stream(const CRS& crs) {
+    if (crs.ctx != ctx) throw Panic("assertion failed: the DeviceRng's key is installed in this CRS's context");
+    return stream++;
+  }
+};
+
 template <class C> struct CommitT {  // commit.rs:18-28
   std::vector<C> coms;
   Matrix<Fr> rand;
@@ -292,6 +316,16 @@ using Commit1 = CommitT<Com1>;
 using Commit2 = CommitT<Com2>;
 
 namespace detail {
+// rows x cols scalars back from a flat array (what the drawn entries return)
+inline Matrix<Fr> fr_matrix(const Bytes& b, size_t rows, size_t cols, size_t at = 0) {
+  Matrix<Fr> m(rows);
+  for (size_t i = 0; i < rows; i++)
+    for (size_t j = 0; j < cols; j++) {
+      const size_t o = (at + i * cols + j) * 32;
+      m[i].push_back(Fr{Bytes(b.begin() + o, b.begin() + o + 32)});
+    }
+  return m;
+}
 template <class Rng> Matrix<Fr> draw(Rng& rng, size_t rows, size_t cols) {
   Matrix<Fr> m(rows);
   for (auto& r : m)
@@ -453,12 +487,42 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     return ok == 1;
   }
 
+  // (the non-template overload is the better match for a DeviceRng)
+  CProof commit_and_prove(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const CRS& crs,
+                          DeviceRng& rng) const {
+    return commit_and_prove_drawn(xvars, yvars, crs, rng);
+  }
   template <class Rng>
   CProof commit_and_prove(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const CRS& crs, Rng& rng) const {
     Commit1 xcoms = batch_commit_x(xvars, crs, rng);
     Commit2 ycoms = batch_commit_y(yvars, crs, rng);
     CProof p{xcoms, ycoms, {}};
     p.equ_proofs.push_back(prove(xvars, yvars, xcoms, ycoms, crs, rng));
+    return p;
+  }
+
+  // commit_and_prove with a DeviceRng: one gs_prove_batch_drawn call; R, S, T come back and are carried
+  template <class Rng>
+  CProof commit_and_prove_drawn(const std::vector<A1>& xvars, const std::vector<A2>& yvars, const CRS& crs,
+                                Rng& rng) const {
+    const size_t m = xvars.size(), n = yvars.size();
+    if (m == 0 || n == 0) throw Panic("index out of bounds: rand[0]");
+    check_statement_shape(m, n);
+    const Ctx& cx = *crs.ctx;
+    const size_t sx = is_scalar<A1>::value ? cx.sz[1] : cx.sz[2], sy = is_scalar<A2>::value ? cx.sz[1] : cx.sz[3];
+    Bytes X = cat(xvars), Y = cat(yvars), A = cat(a_consts), B = cat(b_consts), G = cat(gamma);
+    assert_eq(X.size(), m * sx, "xvars bytes");
+    assert_eq(Y.size(), n * sy, "yvars bytes");
+    assert_eq(A.size(), n * sx, "a_consts bytes");
+    assert_eq(B.size(), m * sy, "b_consts bytes");
+    assert_eq(G.size(), m * n * cx.sz[1], "gamma bytes");
+    Bytes R(m * KX * 32), S(n * KY * 32), T(KY * KX * 32), xc(m * 2 * cx.sz[2]), yc(n * 2 * cx.sz[3]),
+        pi(KX * 2 * cx.sz[3]), th(KY * 2 * cx.sz[2]);
+    cx.chk(gs_prove_batch_drawn(cx.c, (int)TYPE, 1, (int)m, (int)n, X.data(), Y.data(), A.data(), B.data(), G.data(),
+                                rng.next_stream(crs), R.data(), S.data(), T.data(), xc.data(), yc.data(), pi.data(),
+                                th.data()));
+    CProof p{{split<Com1>(xc, m), detail::fr_matrix(R, m, KX)}, {split<Com2>(yc, n), detail::fr_matrix(S, n, KY)}, {}};
+    p.equ_proofs.push_back(EquProof{split<Com2>(pi, KX), split<Com1>(th, KY), TYPE, detail::fr_matrix(T, KY, KX)});
     return p;
   }
 
@@ -546,7 +610,10 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     check_statement_shape(m, n);
     assert_eq(pf.pi.size(), KX, "pi.len()");
     assert_eq(pf.theta.size(), KY, "theta.len()");
-    Matrix<Fr> R1 = detail::draw(rng, m, KX), S1 = detail::draw(rng, n, KY), T1 = detail::draw(rng, KY, KX);
+    // a DeviceRng: R', S', T' are drawn on the device (gs_rerandomize_batch_drawn) and come back with the outputs
+    constexpr bool drawn = std::is_same<Rng, DeviceRng>::value;
+    Matrix<Fr> R1, S1, T1;
+    if constexpr (!drawn) R1 = detail::draw(rng, m, KX), S1 = detail::draw(rng, n, KY), T1 = detail::draw(rng, KY, KX);
     const Ctx& cx = *crs.ctx;
     const size_t sx = is_scalar<A1>::value ? cx.sz[1] : cx.sz[2], sy = is_scalar<A2>::value ? cx.sz[1] : cx.sz[3];
     Bytes A = cat(a_consts), B = cat(b_consts), G = cat(gamma), xc = cat(com_proof.xcoms.coms),
@@ -559,9 +626,17 @@ template <class A1, class A2, class AT, EquType TYPE> struct Equation {
     assert_eq(pi.size(), KX * 2 * cx.sz[3], "pi bytes");
     assert_eq(th.size(), KY * 2 * cx.sz[2], "theta bytes");
     Bytes xo(xc.size()), yo(yc.size()), po(pi.size()), to(th.size());
-    cx.chk(gs_rerandomize_batch(cx.c, (int)TYPE, 1, (int)m, (int)n, A.data(), B.data(), G.data(), xc.data(), yc.data(),
-                                pi.data(), th.data(), R.data(), S.data(), T.data(), xo.data(), yo.data(), po.data(),
-                                to.data()));
+    if constexpr (drawn) {
+      R.resize(m * KX * 32), S.resize(n * KY * 32), T.resize(KY * KX * 32);
+      cx.chk(gs_rerandomize_batch_drawn(cx.c, (int)TYPE, 1, (int)m, (int)n, A.data(), B.data(), G.data(), xc.data(),
+                                        yc.data(), pi.data(), th.data(), rng.next_stream(crs), R.data(), S.data(),
+                                        T.data(), xo.data(), yo.data(), po.data(), to.data()));
+      R1 = detail::fr_matrix(R, m, KX), S1 = detail::fr_matrix(S, n, KY), T1 = detail::fr_matrix(T, KY, KX);
+    } else {
+      cx.chk(gs_rerandomize_batch(cx.c, (int)TYPE, 1, (int)m, (int)n, A.data(), B.data(), G.data(), xc.data(),
+                                  yc.data(), pi.data(), th.data(), R.data(), S.data(), T.data(), xo.data(), yo.data(),
+                                  po.data(), to.data()));
+    }
     CProof out{{split<Com1>(xo, m), {}}, {split<Com2>(yo, n), {}}, {}};
     EquProof np{split<Com2>(po, KX), split<Com1>(to, KY), TYPE, {}};
     if (com_proof.xcoms.rand.size() == m && com_proof.ycoms.rand.size() == n && pf.rand.size() == KY) {
@@ -741,6 +816,12 @@ class Statement {
     items.push_back(std::move(it));
   }
 
+  // With a DeviceRng the statement must hold equations of ONE type (gs_prove_statement_drawn; the mixed calls have no
+  // drawn form, gs_amd.h): R, S once and T per equation are drawn on the device and carried by the result; the
+  // variable groups the type does not use must be empty.
+  StatementProof commit_and_prove(const StatementVars& v, const CRS& crs, DeviceRng& rng) const {
+    return commit_and_prove_drawn(v, crs, rng);
+  }
   template <class Rng> StatementProof commit_and_prove(const StatementVars& v, const CRS& crs, Rng& rng) const {
     StatementProof out;
     out.com_xg = batch_commit_G1(v.xg, crs, rng);
@@ -788,6 +869,48 @@ class Statement {
         out.equ_proofs[p.idx[e]] = EquProof{{pis.begin() + e * kx, pis.begin() + (e + 1) * kx},
                                             {ths.begin() + e * ky, ths.begin() + (e + 1) * ky}, p.ty, Ts[p.idx[e]]};
     }
+    return out;
+  }
+
+  template <class Rng> StatementProof commit_and_prove_drawn(const StatementVars& v, const CRS& crs, Rng& rng) const {
+    if (items.empty()) throw Panic("assertion failed: the statement has an equation");
+    const EquType ty = items[0].ty;
+    for (const Item& it : items)
+      if (it.ty != ty) throw Panic("assertion failed: a DeviceRng proves statements of ONE equation type");
+    const bool xg = xgroup(ty), yg = ygroup(ty);
+    if ((xg ? !v.xs.empty() : !v.xg.empty()) || (yg ? !v.ys.empty() : !v.yg.empty()))
+      throw Panic("assertion failed: the variable groups the type does not use are empty");
+    const Ctx& cx = *crs.ctx;
+    const size_t m = xg ? v.xg.size() : v.xs.size(), n = yg ? v.yg.size() : v.ys.size(), kx = xg ? 2 : 1, ky = yg ? 2 : 1,
+                 E = items.size();
+    if (m == 0 || n == 0) throw Panic("index out of bounds: rand[0]");
+    Bytes X = xg ? cat(v.xg) : cat(v.xs), Y = yg ? cat(v.yg) : cat(v.ys), A, B, G;
+    for (const Item& it : items) {
+      check(it, m, n);
+      A.insert(A.end(), it.A.begin(), it.A.end());
+      B.insert(B.end(), it.B.begin(), it.B.end());
+      G.insert(G.end(), it.G.begin(), it.G.end());
+    }
+    const size_t sx = xg ? cx.sz[2] : cx.sz[1], sy = yg ? cx.sz[3] : cx.sz[1];
+    assert_eq(X.size(), m * sx, "xvars bytes");
+    assert_eq(Y.size(), n * sy, "yvars bytes");
+    assert_eq(A.size(), E * n * sx, "a_consts bytes");
+    assert_eq(B.size(), E * m * sy, "b_consts bytes");
+    assert_eq(G.size(), E * m * n * cx.sz[1], "gamma bytes");
+    Bytes R(m * kx * 32), S(n * ky * 32), T(E * ky * kx * 32), xc(m * 2 * cx.sz[2]), yc(n * 2 * cx.sz[3]),
+        pi(E * kx * 2 * cx.sz[3]), th(E * ky * 2 * cx.sz[2]);
+    cx.chk(gs_prove_statement_drawn(cx.c, (int)ty, E, (int)m, (int)n, X.data(), Y.data(), A.data(), B.data(), G.data(),
+                                    rng.next_stream(crs), R.data(), S.data(), T.data(), xc.data(), yc.data(), pi.data(),
+                                    th.data()));
+    StatementProof out;
+    (xg ? out.com_xg : out.com_xs) = Commit1{split<Com1>(xc, m), detail::fr_matrix(R, m, kx)};
+    (yg ? out.com_yg : out.com_ys) = Commit2{split<Com2>(yc, n), detail::fr_matrix(S, n, ky)};
+    auto pis = split<Com2>(pi, E * kx);
+    auto ths = split<Com1>(th, E * ky);
+    for (size_t e = 0; e < E; e++)
+      out.equ_proofs.push_back(EquProof{{pis.begin() + e * kx, pis.begin() + (e + 1) * kx},
+                                        {ths.begin() + e * ky, ths.begin() + (e + 1) * ky}, ty,
+                                        detail::fr_matrix(T, ky, kx, e * ky * kx)});
     return out;
   }
 
